@@ -11,6 +11,11 @@ pass of the hot path over all bodies: all-pairs force evaluation (N^2 ordered pa
 ranks' target shards) + fused kick/drift (+ the per-step RCCL all-gather of positions when N > 1).
 value = N^2 * K / t, inputs resident in HBM before the timed region.  Total work is fixed as ranks are
 added => "scaling": "strong".
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line can carry:
+the in-kernel clock stamps and this box's VALU ceiling, the committed PMC traffic, the parity block (sampled rows against the
+oracle, every body against the strict fp64 kernel), the leaf-pair kernel figures, per-rank pass times and the CPU baseline.
+--dump-outputs DIR writes the state after the last timed step and the forces on it as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -33,6 +38,8 @@ PEAK_FP32_TFLOPS = 157.3           # MI355X_MICROARCH.md: peak FP32 vector = FP3
 HBM_PEAK_GBPS = 8000.0
 PROFILE_ROUNDS = ("r5", "r4")      # profiles/<round>/pmc_force_kernel.json, newest first: the committed PMC passes of this command
 SHADER_PEAK_MHZ = 2400.0           # MI355X_MICROARCH.md: the clock the 157.3 TFLOP/s figure assumes
+DUMP_BUDGET_BYTES = 64 * 10**6     # --dump-outputs: at most this much .npy data per run, headers included
+DUMP_SAMPLE_SEED = 20240601        # the fixed sample of bodies written when the whole state would not fit
 
 
 def host_facts():
@@ -258,6 +265,43 @@ def _norm(a):
     return np.sqrt((a * a).sum(axis=1))
 
 
+def dump_outputs(out_dir, system, bodies, G, dim, world, rank, dist):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, in fp64 -- positions.npy and
+    velocities.npy (the state after the last kick/drift) -- and forces.npy: the step's force pass once more, on that state (a
+    step hands back no forces, and at the reference's G they move the fp64 state too little to show in it).
+    When all N rows would exceed DUMP_BUDGET_BYTES, the same fixed, seeded sample of bodies goes into every file and
+    rows.npy lists their indices.  Collective for world > 1 (every rank calls it); rank 0 writes."""
+    import numpy as np
+    n = bodies.shape[0]
+    per_row = 3 * dim * 8
+    headers = 4 * 4096                                  # generous: an .npy header is 128 bytes
+    sampled = n * per_row > DUMP_BUDGET_BYTES - headers
+    if sampled:
+        k = (DUMP_BUDGET_BYTES - headers) // (per_row + 8)
+        sel = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+    else:
+        sel = np.arange(n)
+    state = system.gather_bodies(bodies)                # collective for world > 1
+    system.compute_forces()                             # the next step's force pass (exchange included)
+    lo, hi = system.layout.bounds()
+    mine = sel[(sel >= lo) & (sel < hi)]
+    part = system.forces(G)[mine - lo]                  # this rank's targets
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, part)             # ranks hold consecutive shards: rank order = row order
+        forces = np.concatenate(parts)
+    else:
+        forces = part
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"positions": state[sel, :dim], "velocities": state[sel, dim:2 * dim], "forces": forces}
+    if sampled:
+        arrays["rows"] = sel
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def parity_block(system, bodies, G, args, world, rank, dist, refine_tol=1.0e-5):
     """BASELINE metric, second half, for ANY number of ranks -- run by every rank after the timed region.
     (1) SURVEY 8d protocol: >= 1,024 sampled target rows (all rows at N <= 65,536) of one sharded force evaluation on the
@@ -406,6 +450,12 @@ def main():
                     help="bodies of the CPU baseline's sample (0: automatic, ~10 s of host time = 131,072 on a GPU box's 16 threads; "
                          "SURVEY 8(d) names 262,144 or the full N -- minutes, for profiles/, not for the driver's default run)")
     ap.add_argument("--cpu-baseline-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: clock stamps and VALU ceiling, PMC traffic, parity block, leaf-pair figures, "
+                         "per-rank pass times and the CPU baseline (--no-all-bodies / --no-cpu-baseline trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step (positions, velocities) and the forces on it as DIR/<name>.npy "
+                         "(fp64, <= 64 MB: a fixed sample of bodies above that)")
     args = ap.parse_args()
     if args.cpu_baseline_child:
         cpu_baseline_child(args.cpu_baseline_child, args.bodies, args.dim, args.seed)
@@ -501,18 +551,19 @@ def main():
             dist.destroy_process_group()
             sys.exit(3)
 
-    # the force kernel's workgroups stamp the shader clock they held (nbx_ctx_enable_clock_stamps: two scalar clock reads and
-    # one 16-byte store per workgroup of ~40 ms); on before the warm-up so that the captured step carries it
-    clock_stamps = True
-    try:
-        be.ctx.enable_clock_stamps(True)
-    except nbx.NbxError:   # a variant without stamps was asked for
-        clock_stamps = False
+    # --full: the force kernel's workgroups stamp the shader clock they held (nbx_ctx_enable_clock_stamps: two scalar clock reads
+    # and one 16-byte store per workgroup of ~40 ms); on before the warm-up so that the captured step carries it
+    clock_stamps = args.full
+    if clock_stamps:
+        try:
+            be.ctx.enable_clock_stamps(True)
+        except nbx.NbxError:   # a variant without stamps was asked for
+            clock_stamps = False
     for _ in range(args.warmup):
         system.step(args.dt, G, 1)
     sync_all()
     be.kernel_time()  # reset the force-kernel event log
-    if world > 1:
+    if world > 1 and args.full:
         be.enable_timing(True)   # events around LOCAL / REMOTE (compute stream) and the exchange (comm stream)
     sync_all()
     t0 = time.perf_counter()
@@ -520,7 +571,7 @@ def main():
     sync_all()
     elapsed = time.perf_counter() - t0
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = dict(be.pass_times(), rank=rank, device=local_rank, targets=int(system.layout.count), wall_s=elapsed)
         gathered = [None] * world
         dist.all_gather_object(gathered, mine)
@@ -539,8 +590,10 @@ def main():
         except nbx.NbxError:
             held = None
         be.ctx.enable_clock_stamps(False)
+    if args.dump_outputs:          # before anything below moves the bodies or evaluates forces again
+        dump_outputs(args.dump_outputs, system, bodies, G, args.dim, world, rank, dist)
     ceiling = None
-    if rank == 0:   # the same chip, straight after the timed steps (still warm): a pure v_pk_fma_f32 stream for ~50 ms
+    if rank == 0 and args.full:    # the same chip, straight after the timed steps (still warm): a pure v_pk_fma_f32 stream for ~50 ms
         try:
             tf, mhz = nbx.package.capi.measure_valu_ceiling(local_rank, 50.0)
             ceiling = {"tflops": tf, "shader_mhz": mhz}
@@ -582,7 +635,8 @@ def main():
                          # lane pair per cycle; the chip clocks lower under a dense VALU load, and by how much differs from box to box
                          "shader_mhz": held["median_mhz"] if held else None,
                          "shader_mhz_detail": dict(held, source="in-kernel stamps (s_memtime / s_memrealtime) of the last timed force launch, "
-                                                   "one pair per workgroup, nbx_ctx_shader_clock") if held else "not measured (kernel variant without stamps)",
+                                                   "one pair per workgroup, nbx_ctx_shader_clock") if held else
+                                                   ("not measured (kernel variant without stamps)" if args.full else "not measured (--full)"),
                          "frac_at_held_clock": achieved_tflops / (PEAK_FP32_TFLOPS * held["median_mhz"] / SHADER_PEAK_MHZ) if held else None,
                          "this_box_ceiling": dict(ceiling, kernel="pure v_pk_fma_f32 stream, 16 chains per lane, every CU full, ~50 ms right after the "
                                                   "timed steps (nbx_measure_valu_ceiling)") if ceiling else None,
@@ -592,7 +646,7 @@ def main():
                                  "achieved_GBps": (28.0 * N if world == 1 else (16.0 * N + 12.0 * system.layout.count)) / kern_s_per_step / 1e9,
                                  "peak_GBps": HBM_PEAK_GBPS}},
         }
-    if rank == 0 and world == 1 and N == 1 << 20 and args.dim == 3:
+    if rank == 0 and world == 1 and N == 1 << 20 and args.dim == 3 and args.full:
         # HBM traffic of the force kernel per launch: PMC counters cannot be read from inside the process; they come from
         # the committed rocprofv3 --pmc passes of this same command (tools/profile_bench.sh -> tools/summarize_prof.py ->
         # profiles/<round>/pmc_force_kernel.json), and only if that profile is of the kernel that just ran -- identified by the
@@ -632,11 +686,11 @@ def main():
         result["per_rank"] = per_rank
         result["upload"] = {"bytes_over_this_ranks_host_link": be.upload_bytes, "whole_array_bytes": int(bodies.size * 8),
                             "how": "own shard host-to-device; other shards' masses by one all-gather, positions by the step's exchange"}
-        result["exchange_hidden_behind_local_pass"] = all(bool(r["exchange_hidden"]) for r in per_rank)
+        result["exchange_hidden_behind_local_pass"] = all(bool(r["exchange_hidden"]) for r in per_rank) if per_rank else None
     if world > 1:
         dist.barrier()
     acc = None
-    if not args.no_cpu_baseline:   # parity of THIS run, whatever the rank count (every rank takes part; rank 0 holds the result)
+    if args.full and not args.no_cpu_baseline:   # parity of THIS run, whatever the rank count (every rank takes part; rank 0 holds the result)
         acc = parity_block(system, bodies, G, args, world, rank, dist)
     if world > 1:
         dist.barrier()             # the last collective: rank 0's CPU-side work below holds nobody in a barrier

@@ -24,9 +24,27 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
+    """The reference's own object code where oracle/build_ref.sh built it; elsewhere its recorded answers to the calls the
+    tests make (tests/golden/ref_calls_*.npz).  NBODY_RECORD_REFERENCE_CALLS=<dir> records them (tests/golden/make_golden.py calls)."""
+    from oracle_lib import RecordedReference, RecordingReference, Reference, have_reference
+    if not have_reference():
+        yield RecordedReference()
+        return
+    out = os.environ.get("NBODY_RECORD_REFERENCE_CALLS")
+    if not out:
+        yield Reference()
+        return
+    rec = RecordingReference(Reference())
+    yield rec
+    rec.save(out)
+
+
+@pytest.fixture(scope="session")
+def reference_library():
+    """Tests that time or run the reference's object code itself: nothing recorded can stand in for it."""
     from oracle_lib import Reference, have_reference
     if not have_reference():
-        pytest.skip("oracle/_ref/libnbody_ref.so not built (needs /root/reference; see oracle/build_ref.sh)")
+        pytest.skip("oracle/_ref/libnbody_ref.so not built (needs the reference's sources; see oracle/build_ref.sh)")
     return Reference()
 
 

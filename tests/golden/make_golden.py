@@ -17,6 +17,9 @@ see oracle/ref_driver.cpp) -- data, not source.  Files are numpy .npz (no pickle
   bvh_leaves_D3_N3000.npz        own BVH<D>(bodies, 16) read through its public root (bvh.h:91-103, bvh.cpp:16-126) as CSR arrays,
                                  and per body the sum over all leaves of BVH<D>::calculate_force(body, leaf) (bvh.cpp:143-176):
                                  the tree codes' near-field sums on a reference-built tree (N = 3000: ragged leaves of 11-12)
+  ref_calls_<k>.npz              (python tests/golden/make_golden.py calls) the reference's answer to every call the CPU tests
+                                 make through their `reference` fixture (tests/oracle_lib.py RecordingReference), replayed where
+                                 oracle/_ref is absent
 """
 import os
 import subprocess
@@ -67,9 +70,23 @@ def bvh(ref):
                             forces_bvh_all_leaves=ref.bvh_leaf_forces(b, 16))
 
 
+def calls():
+    """Run the tests that take the `reference` fixture against the live reference, recording its answers."""
+    for old in os.listdir(HERE):
+        if old.startswith("ref_calls_") and old.endswith(".npz"):
+            os.remove(os.path.join(HERE, old))
+    env = dict(os.environ, NBODY_RECORD_REFERENCE_CALLS=HERE)
+    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "-m", "not gpu",
+                           os.path.join(ROOT, "tests", "test_oracle_vs_ref.py"), os.path.join(ROOT, "tests", "test_leaf_pairs_cpu.py")],
+                          cwd=ROOT, env=env)
+
+
 def main():
     subprocess.check_call([os.path.join(ROOT, "oracle", "build_ref.sh")])
     os.environ.setdefault("OMP_NUM_THREADS", "8")
+    if len(sys.argv) > 1 and sys.argv[1] == "calls":
+        calls()
+        return
     ref = Reference()
     if len(sys.argv) > 1 and sys.argv[1] == "octree":
         octree(ref)

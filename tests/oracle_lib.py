@@ -241,6 +241,137 @@ def have_reference() -> bool:
     return os.path.exists(REF_SO)
 
 
+# ---- the reference's outputs for the calls the tests make, recorded where its object code exists -------------------------
+# tests/golden/ref_calls_*.npz (python tests/golden/make_golden.py calls): one array per call, keyed by the method and a digest
+# of its arguments.  Where oracle/_ref is absent the tests' `reference` fixture replays them: same answers, no reference needed.
+REF_CALLS_GLOB = os.path.join(ROOT, "tests", "golden", "ref_calls_*.npz")
+REF_CALLS_CHUNK = 900 * 1024          # bytes of raw array data per file (committed files stay under 1 MiB)
+
+
+def _call_key(name, args):
+    import hashlib
+    h = hashlib.sha1()
+    for a in args:
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a)
+            h.update(f"{a.dtype.str}{a.shape}".encode())
+            h.update(a.tobytes())
+        else:
+            h.update(repr(a).encode())
+    return f"{name}__{h.hexdigest()[:24]}"
+
+
+class RecordedReference:
+    """The Reference interface the CPU tests use, answered from the recorded outputs.  A call that was not recorded fails."""
+
+    def __init__(self):
+        import glob
+        self.rec = {}
+        for path in sorted(glob.glob(REF_CALLS_GLOB)):
+            with np.load(path, allow_pickle=False) as z:
+                self.rec.update({k: z[k] for k in z.files})
+        if not self.rec:
+            raise FileNotFoundError(REF_CALLS_GLOB)
+        self.omp_threads = int(self.rec["omp_threads"])     # brute_force(1, ...) partitions its sums by this thread count
+
+    def _get(self, name, *args):
+        key = _call_key(name, args)
+        if key not in self.rec:
+            raise KeyError(f"no recorded reference output for {name}{tuple(a.shape if isinstance(a, np.ndarray) else a for a in args)}; "
+                           "re-record with tests/golden/make_golden.py calls")
+        return self.rec[key].copy()
+
+    def G(self):
+        return float(self._get("G"))
+
+    def sizeof_body(self, dim):
+        return int(self._get("sizeof_body", dim))
+
+    def generate(self, seed, n, dim):
+        return self._get("generate", seed, n, dim)
+
+    def brute_force(self, variant, bodies):
+        return self._get("brute_force", variant, bodies)
+
+    def octree_direct_forces(self, bodies):
+        return self._get("octree_direct_forces", bodies)
+
+    def bvh_leaves(self, bodies, max_bodies=16):
+        return self._get("bvh_leaves.offsets", bodies, max_bodies), self._get("bvh_leaves.bodies", bodies, max_bodies)
+
+    def bvh_leaf_forces(self, bodies, max_bodies=16):
+        return self._get("bvh_leaf_forces", bodies, max_bodies)
+
+    def update_body_velocities(self, bodies, forces, dt):
+        bodies[...] = self._get("update_body_velocities", bodies, forces, float(dt))
+
+    def update_body_positions(self, bodies, dt):
+        bodies[...] = self._get("update_body_positions", bodies, float(dt))
+
+    def compute_accuracy(self, forces, ref):
+        return float(self._get("compute_accuracy", forces, ref))
+
+
+class RecordingReference:
+    """Wraps the live Reference: answers as it does and keeps every answer under RecordedReference's keys (save() writes them)."""
+
+    def __init__(self, ref):
+        self.ref = ref
+        self.rec = {"omp_threads": np.int64(Oracle().num_threads())}     # one OpenMP runtime per process: the reference's count
+
+    def _keep(self, name, args, out):
+        self.rec[_call_key(name, args)] = np.asarray(out)
+        return out
+
+    def G(self):
+        return self._keep("G", (), self.ref.G())
+
+    def sizeof_body(self, dim):
+        return self._keep("sizeof_body", (dim,), self.ref.sizeof_body(dim))
+
+    def generate(self, seed, n, dim):
+        return self._keep("generate", (seed, n, dim), self.ref.generate(seed, n, dim))
+
+    def brute_force(self, variant, bodies):
+        return self._keep("brute_force", (variant, bodies), self.ref.brute_force(variant, bodies))
+
+    def octree_direct_forces(self, bodies):
+        return self._keep("octree_direct_forces", (bodies,), self.ref.octree_direct_forces(bodies))
+
+    def bvh_leaves(self, bodies, max_bodies=16):
+        offs, idx = self.ref.bvh_leaves(bodies, max_bodies)
+        self._keep("bvh_leaves.offsets", (bodies, max_bodies), offs)
+        return offs, self._keep("bvh_leaves.bodies", (bodies, max_bodies), idx)
+
+    def bvh_leaf_forces(self, bodies, max_bodies=16):
+        return self._keep("bvh_leaf_forces", (bodies, max_bodies), self.ref.bvh_leaf_forces(bodies, max_bodies))
+
+    def update_body_velocities(self, bodies, forces, dt):
+        key_args = (bodies.copy(), forces, float(dt))
+        self.ref.update_body_velocities(bodies, forces, dt)
+        self._keep("update_body_velocities", key_args, bodies.copy())
+
+    def update_body_positions(self, bodies, dt):
+        key_args = (bodies.copy(), float(dt))
+        self.ref.update_body_positions(bodies, dt)
+        self._keep("update_body_positions", key_args, bodies.copy())
+
+    def compute_accuracy(self, forces, ref):
+        return self._keep("compute_accuracy", (forces, ref), self.ref.compute_accuracy(forces, ref))
+
+    def save(self, directory):
+        """ref_calls_<k>.npz, each holding at most REF_CALLS_CHUNK bytes of arrays."""
+        chunks, cur, size = [], {}, 0
+        for k, v in sorted(self.rec.items()):
+            if cur and size + v.nbytes > REF_CALLS_CHUNK:
+                chunks.append(cur)
+                cur, size = {}, 0
+            cur[k], size = v, size + v.nbytes
+        chunks.append(cur)
+        for i, c in enumerate(chunks):
+            np.savez_compressed(os.path.join(directory, f"ref_calls_{i}.npz"), **c)
+
+
 # ---- the stated fp32 tolerance (DESIGN.md section 4), FROZEN in round 3 from all-bodies evidence ---------------------
 # The device sums N fp32 pair terms; the oracle is the reference's fp64 sequential path fed the same fp32-rounded inputs.
 # For body i let F_i be the oracle force, S_i = sum_j |f_ij| the sum of pair-force magnitudes and kappa_i = S_i/|F_i| the

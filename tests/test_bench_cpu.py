@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -64,7 +65,7 @@ def test_plain_gpus_n_starts_the_ranks_as_a_child_process():
     assert p.stderr.count("bench.py needs a GPU") >= 2, p.stderr[-2000:]
 
 
-def test_cpu_baseline_leg_runs_its_solvers_in_child_processes(reference):
+def test_cpu_baseline_leg_runs_its_solvers_in_child_processes(reference_library):
     """bench.py's cpu_baseline on a small sample: the reference's object code, one fresh process per thread count (OpenMP sizes its
     pool at start-up), both solvers reported in ordered pairs per second, the --cpu-baseline-n override honoured."""
     out = bench.cpu_baseline(8192, 3, 1, budget_s=0.05, n_sample=3000)
@@ -72,3 +73,53 @@ def test_cpu_baseline_leg_runs_its_solvers_in_child_processes(reference):
     assert [r["n"] for r in out["all_runs"]][:2] == [3000, 3000]
     assert {r["solver"] for r in out["all_runs"]} == {"brute_force_omp_n_body_2<3>", "brute_force_omp_n_body_1<3>"}
     assert "first 3000 bodies" in out["sample"]
+
+
+class _OneRank:
+    """The calls dump_outputs makes on a one-rank system: layout.bounds, gather_bodies (state), compute_forces and forces."""
+
+    def __init__(self, state, forces):
+        self.state, self.f, self.computed = state, forces, False
+        self.layout = types.SimpleNamespace(bounds=lambda: (0, state.shape[0]))
+
+    def gather_bodies(self, bodies):
+        return self.state.copy()
+
+    def compute_forces(self):
+        self.computed = True
+
+    def forces(self, G):
+        assert self.computed
+        return self.f.copy()
+
+
+def _dump(tmp_path, n, dim):
+    import numpy as np
+    rng = np.random.default_rng(7)
+    state, forces = rng.standard_normal((n, 2 * dim + 1)), rng.standard_normal((n, dim))
+    out = tmp_path / f"dump_{n}_{dim}"
+    bench.dump_outputs(str(out), _OneRank(state, forces), state, 1.0, dim, 1, 0, None)
+    return out, state, forces
+
+
+def test_dump_outputs_writes_the_whole_state_when_it_fits(tmp_path):
+    import numpy as np
+    out, state, forces = _dump(tmp_path, 5000, 3)
+    assert sorted(os.listdir(out)) == ["forces.npy", "positions.npy", "velocities.npy"]
+    for name, want in (("positions", state[:, :3]), ("velocities", state[:, 3:6]), ("forces", forces)):
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want)
+
+
+def test_dump_outputs_of_2_to_the_20_bodies_is_a_fixed_sample_within_64_mb(tmp_path):
+    import numpy as np
+    n = 1 << 20
+    out, state, forces = _dump(tmp_path, n, 3)
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 10**6
+    rows = np.load(out / "rows.npy")
+    assert rows.dtype == np.float64 and rows.size > n // 2 and np.all(np.diff(rows) > 0)
+    idx = rows.astype(np.int64)
+    assert np.array_equal(np.load(out / "forces.npy"), forces[idx])
+    assert np.array_equal(np.load(out / "positions.npy"), state[idx, :3])
+    again, _, _ = _dump(tmp_path / "again", n, 3)
+    assert np.array_equal(np.load(again / "rows.npy"), rows)       # the same rows from run to run

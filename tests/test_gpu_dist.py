@@ -87,7 +87,7 @@ def test_bench_line_for_two_ranks_carries_parity(tmp_path):
     import subprocess
     env = dict(os.environ, NBODY_BENCH_BACKEND="gloo", NBODY_BENCH_DEVICE="0", OMP_NUM_THREADS="8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--bodies", "32768"]
     p = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -1,7 +1,8 @@
 """CPU: SURVEY 8(f-4), the leaf-pair direct-sum oracle (oracle_leaf_pair_forces) and its host-side plumbing.
 Law 1 (tree leaf) is pinned twice: to the reference's own Barnes-Hut octree walked with theta = 0, and to the reference's own
 BVH -- the leaves of BVH<D>(bodies, 16) read through its public root, and per body the sum of BVH::calculate_force(body, leaf)
-over all of them (bvh.cpp:143-176) -- live where oracle/_ref exists, and through committed golden outputs everywhere;
+over all of them (bvh.cpp:143-176) -- live where oracle/_ref exists (elsewhere through its recorded answers), and through
+committed golden outputs everywhere;
 law 0 is the brute-force oracle again; law 2 (FMM P2P) is a restatement only (PARITY UNPINNED: executing FMM_Parlay is
 undefined behaviour -- its constructor leaves the tree pointing into a destroyed vector, fmm_parlay.cpp:16-22 -- so the
 reference cannot produce a vector to pin it to; see the oracle)."""

@@ -11,7 +11,7 @@ tail -4 $O/gpu_tests_run.log
 cp gpurun_out/accuracy_all_bodies.jsonl $O/accuracy_all_bodies.jsonl
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 1; }
 cat $O/bench_full.json
 timeout -k 10 500 bash tools/profile_bench.sh check > $O/profile_bench.log 2>&1 || { tail -20 $O/profile_bench.log; exit 1; }
 for shape in 5 bvh16; do
