@@ -261,15 +261,19 @@ int nbx_ctx_step(nbx_ctx* ctx, double G, double dt, int nsteps);
  * sharded form is nbx_node_step_kdk.  (nbx_ctx_step is the reference helpers' plain order, kick then drift: first order.) */
 int nbx_ctx_step_kdk(nbx_ctx* ctx, double G, double dt, int nsteps);
 
-/* Forces of this shard's targets as Vector<dim>[shard_len] doubles: F_i = -(G m_i) a_i.
+/* Forces of this shard's targets as Vector<dim>[count] doubles: F_i = -(G m_i) a_i.  count = this shard's bodies: shard_len, or
+ * fewer -- possibly none -- for the last shards (a shard g with g * shard_len >= n_total is empty); exactly count rows are written.
  * Synchronises the stream. */
 int nbx_ctx_get_forces(nbx_ctx* ctx, double G, double* forces_out);
 /* The reference's accuracy metric (utils.h:170-219, ACCURACY_PCT_THRESHOLD 1 %, ACCURACY_FORCE_THRESHOLD 1e-20)
- * evaluated on the device against reference_forces (host, Vector<dim>[shard_len] of this shard): percent of
- * bodies whose every force component is within 1 % (absolute 1e-9 where |ref| < 1e-20).  The device forces are
+ * evaluated on the device against reference_forces (host, Vector<dim>[count] of this shard: count rows are read): percent of
+ * bodies whose every force component is within 1 % (absolute 1e-9 where |ref| < 1e-20).  An empty shard (count = 0) reads
+ * nothing and reports 0.0, as the reference's compute_accuracy does for no bodies.  The device forces are
  * never copied back; 4 bytes return.  Synchronises the stream. */
 int nbx_ctx_accuracy(nbx_ctx* ctx, double G, const double* reference_forces, double* percent);
-/* Raw fp32 accelerations, SoA float[dim][shard_len].  Synchronises the stream. */
+/* Raw fp32 accelerations, SoA float[dim][count] (component k of target l at accel_out[k * count + l]; count as for
+ * nbx_ctx_get_forces -- the last shard's rows are packed, not spaced shard_len apart): the fp32 rounding of the fp64 sum of the
+ * slices' partial sums that nbx_ctx_get_forces scales by -(G m).  Synchronises the stream. */
 int nbx_ctx_get_accel(nbx_ctx* ctx, float* accel_out);
 /* Write this shard's positions and velocities (fp64 state) back into the caller's full-length
  * Body<dim> array (only entries [shard*shard_len, ...) are touched).  Synchronises the stream. */
@@ -345,7 +349,7 @@ int nbx_ctx_set_refine(nbx_ctx* ctx, double rel_tolerance, double sigma_factor);
 /* After a mixed-mode force evaluation: selected = targets the rule listed, refined = those re-evaluated in fp64
  * (the same number: there is no capacity to overflow).  Either pointer may be NULL.  Synchronises the stream. */
 int nbx_ctx_refine_stats(nbx_ctx* ctx, unsigned* selected, unsigned* refined);
-/* The per-target statistic the last force evaluation wrote beside the accelerations, double[shard_len]:
+/* The per-target statistic the last force evaluation wrote beside the accelerations, double[count] (count as for nbx_ctx_get_forces):
  *   mixed mode:                  Q_i = sum over the source blocks of |block partial sum|^2 (what the selection rule thresholds);
  *   variant "strict_f64_t4_mag": S_i = sum_j |a_ij|, the sum of the pair terms' magnitudes (the yardstick of a cancelling
  *                                sum's error: backward error = |da_i| / S_i, condition number kappa_i = S_i / |a_i|).

@@ -217,10 +217,11 @@ hipError_t launch_refine(int dim, const RefineLaunch& R, hipStream_t stream) {
         (unsigned)R.strict_slices > a.total_tiles || R.strict_budget < (unsigned long long)dim * R.base.pad)
         return hipErrorInvalidValue;
     a.tiles_per_split = 0;   // the fp64 pass derives its own from the list's length
+    // the list's length, which nbx_ctx_refine_stats reads back: zero for an empty shard too (the counters may be a reused block's)
+    if ((e = hipMemsetAsync(a.counters + 3, 0, sizeof(unsigned), stream)) != hipSuccess) return e;
     if (a.count == 0) return hipSuccess;
     const int di = dim - 2;
     const dim3 block(256, 1, 1);
-    if ((e = hipMemsetAsync(a.counters + 3, 0, sizeof(unsigned), stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(table().ck.refine_select[di], dim3((a.count + 63u) / 64u, 1, 1), block, 0, stream, a);   // four lanes per target
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // listed targets x strict slices; a workgroup whose list block does not exist returns at once

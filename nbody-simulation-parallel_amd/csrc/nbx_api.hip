@@ -767,6 +767,10 @@ int nbx_ctx_upload_bodies(nbx_ctx* c, const void* bodies, size_t stride_bytes) {
 int nbx_ctx_upload_shard(nbx_ctx* c, const void* shard_bodies, size_t stride_bytes, double* max_abs_mass, double* max_abs_coord) {
     if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
     if (!shard_bodies && c->count) return fail(NBX_ERR_INVALID, "null argument");
+    // a refused stride leaves the context as it was (upload_stage would refuse it too, but only after the context is marked stale)
+    const size_t min_stride = (size_t)(2 * c->dim + 1) * sizeof(double);
+    if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
+        return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
     unsigned long long facts[3] = {0, 0, 0};
     c->uploaded = false;
     // a rank whose shard is empty still packs its (all-pad) chunk: massless bodies at the origin
