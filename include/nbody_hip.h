@@ -176,7 +176,7 @@ int nbx_leaf_plan_forces_ctx(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double 
 int nbx_leaf_plan_get_forces(nbx_leaf_plan* plan, double* forces_out);
 /* update_body_velocities + update_body_positions (methods.cpp:425-450) of `ctx`'s bodies from the LAST evaluation's leaf sums
  * (law and G as given there), fp64, the arithmetic of nbx_ctx_kick_drift; bodies in no leaf drift with their velocity.
- * Asynchronous on the context's stream.  This is the stepping loop of a tree code whose far field is zero: what `nbody_sim
+ * Asynchronous on the context's stream.  This is the stepping loop of a tree code (its far field: nbx_leaf_plan_set_cells; without cells it is zero): what `nbody_sim
  * -m p --steps k` runs. */
 int nbx_leaf_plan_kick_drift(nbx_leaf_plan* plan, nbx_ctx* ctx, double dt);
 /* nsteps x { nbx_leaf_plan_forces_ctx(plan, ctx, law, G, NULL, NULL); nbx_leaf_plan_kick_drift(plan, ctx, dt) } with the structure
@@ -190,6 +190,39 @@ int nbx_leaf_plan_step(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, dou
 int nbx_leaf_plan_time_kernel(nbx_leaf_plan* plan, int law, int reps, float* mean_ms);
 /* Counts of the layout: padded slots, copy runs, workgroups, wave64 per workgroup (any pointer may be NULL). */
 int nbx_leaf_plan_info(const nbx_leaf_plan* plan, size_t* slots, size_t* runs, size_t* workgroups, int* waves_per_workgroup);
+
+/* ---- the far field of a plan: cells and far lists -----------------------------------------------------------------------
+ * The other half of the reference's tree codes: a body is attracted by a far node as by ONE pseudo-body of the node's total mass
+ * at its centre of mass (octree.cpp:129-151, bvh.cpp:203-239).  A plan may carry CELLS and, per target leaf, a FAR LIST of cells;
+ * every evaluation (nbx_leaf_plan_forces, _forces_ctx, _step) then, on the evaluation's stream: gathers the positions, computes
+ * every cell's mass and centre of mass from the positions as they stand NOW, runs the pair kernel, and adds, for every body of
+ * every target leaf t and every cell c on t's far list, the law's pair term with the pseudo-body (com_c, M_c) as the source into the
+ * same slot-ordered sums -- so nbx_leaf_plan_get_forces / _kick_drift / _step carry near + far without further change.  A plan
+ * without cells behaves bit for bit as before.
+ *   cell_first_leaf[n_cells], cell_leaf_count[n_cells]: cell c = leaves [first, first + count) -- with leaves numbered depth-first
+ *       (or in Morton order) every node of a tree is such a range.  Cells may nest, overlap, be empty or cover only empty leaves.
+ *   far_offsets[n_leaves + 1], far_cells[far_offsets[n_leaves]]: CSR over target leaves like the source lists; entries are summed
+ *       in a fixed order, a repeated entry counts twice; a leaf may have a far list and no near list or the other way round.
+ *   moments: M_c = sum m_j, com_c = sum m_j p_j / M_c over the bodies of the cell's leaves, in fp64 from the fp32 slot values
+ *       (per-leaf sums first, then each cell sums its leaves': fixed order, no atomics, an error that does not grow with N; the tests
+ *       hold the centre of mass to 2^-30 of the cell's largest coordinate and the mass to 2^-30 M, 1/64 of an fp32 ulp).  A cell with M_c == 0 contributes exactly
+ *       zero, never a NaN (bvh.cpp:225 guards the same case).
+ *   law: the evaluation's law applied to the pseudo-body as if it were a body -- same sign, same rule below the law's threshold.
+ *       (The reference's far branches skip only at dist < 1e-9 and recurse otherwise; a cell that close to a target is on no
+ *       sensible far list.)  The pseudo-body is fp32 on the device, like every source.
+ * NBX_ERR_INVALID, before anything is launched, when a cell's range runs past n_leaves, a far entry is >= n_cells, the offsets do
+ * not start at 0 or decrease, or a pointer needed for a non-empty array is null; the plan then keeps its previous cells.
+ * Replaces the plan's cells and far lists (n_cells = 0 removes them; the other pointers may then be NULL); the arrays are copied
+ * (4 bytes per far entry go to the device); the call waits for the plan's last evaluation and for its own copies. */
+int nbx_leaf_plan_set_cells(nbx_leaf_plan* plan, const uint32_t* cell_first_leaf, const uint32_t* cell_leaf_count, size_t n_cells,
+                            const uint32_t* far_offsets, const uint32_t* far_cells);
+/* Moments of the LAST evaluation as the far pass used them, before the fp32 rounding: mass_out[n_cells], com_out[n_cells * dim]
+ * (centre of mass of a massless cell: zeros).  Either pointer may be NULL.  Synchronises.  NBX_ERR_STATE before the first
+ * evaluation with these cells; a plan without cells writes nothing. */
+int nbx_leaf_plan_get_cells(nbx_leaf_plan* plan, double* mass_out, double* com_out);
+/* Counts, and the device time of the last evaluation's moment and far kernels when that evaluation was timed (kernel_ms != NULL;
+ * 0 otherwise); kernel_ms of the evaluation itself keeps meaning the near-field pair kernel.  Any pointer may be NULL. */
+int nbx_leaf_plan_cell_info(nbx_leaf_plan* plan, size_t* n_cells, size_t* far_entries, float* moments_ms, float* far_ms);
 
 /* ---- device-resident context ------------------------------------------------------------------
  * A context owns the targets of ONE shard of an N-body system on ONE device and a full-length

@@ -50,6 +50,9 @@ ABI = [
     ("nbx_leaf_plan_step", _i, [_vp, _vp, _i, _d, _d, _i]),
     ("nbx_leaf_plan_time_kernel", _i, [_vp, _i, _i, _pf]),
     ("nbx_leaf_plan_info", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz), _pi]),
+    ("nbx_leaf_plan_set_cells", _i, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("nbx_leaf_plan_get_cells", _i, [_vp, _vp, _vp]),
+    ("nbx_leaf_plan_cell_info", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _pf, _pf]),
     ("nbx_ctx_create", _i, [_c.POINTER(_vp), _i, _i, _sz, _i, _i]),
     ("nbx_ctx_destroy", _i, [_vp]),
     ("nbx_ctx_set_stream", _i, [_vp, _vp]),
@@ -348,6 +351,30 @@ class LeafPlan:
     def step(self, ctx: "Context", law: int, G: float, dt: float, nsteps: int):
         """nsteps x {forces_ctx(fetch=False); kick_drift} in one call (nbx_leaf_plan_step)."""
         self._ck(self.lib.nbx_leaf_plan_step(self.h, ctx.h, int(law), float(G), float(dt), int(nsteps)), "nbx_leaf_plan_step")
+
+    def set_cells(self, cell_first_leaf, cell_leaf_count, far_offsets, far_cells):
+        """The plan's far field (nbx_leaf_plan_set_cells): cells as leaf ranges and a CSR far list per target leaf; every evaluation
+        then adds the cells' monopole terms, with moments recomputed on the device.  Empty cell arrays remove the far field."""
+        arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in (cell_first_leaf, cell_leaf_count, far_offsets, far_cells)]
+        if arrs[0].size != arrs[1].size:
+            raise ValueError("cell_first_leaf and cell_leaf_count must have n_cells entries each")
+        ptr = [a.ctypes.data if a.size else None for a in arrs]
+        self._ck(self.lib.nbx_leaf_plan_set_cells(self.h, ptr[0], ptr[1], arrs[0].size, ptr[2], ptr[3]), "nbx_leaf_plan_set_cells")
+        self.n_cells = int(arrs[0].size)
+
+    def cells(self):
+        """(mass[n_cells], com[n_cells, dim]) of the last evaluation, fp64, as the far pass used them (nbx_leaf_plan_get_cells)."""
+        n_cells = self.cell_info()[0]
+        mass, com = np.zeros(n_cells, dtype=np.float64), np.zeros((n_cells, self.dim), dtype=np.float64)
+        self._ck(self.lib.nbx_leaf_plan_get_cells(self.h, mass.ctypes.data if n_cells else None, com.ctypes.data if n_cells else None),
+                 "nbx_leaf_plan_get_cells")
+        return mass, com
+
+    def cell_info(self):
+        """(cells, far entries, moment pass ms, far pass ms); the times are those of the last evaluation if it was timed, else 0."""
+        a, b, m, f = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._ck(self.lib.nbx_leaf_plan_cell_info(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(m), ctypes.byref(f)), "nbx_leaf_plan_cell_info")
+        return a.value, b.value, m.value, f.value
 
     def time_kernel(self, law: int, reps: int) -> float:
         """Measurement: mean ms of the second half of `reps` back-to-back launches of the pair kernel."""

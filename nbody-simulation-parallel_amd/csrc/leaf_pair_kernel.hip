@@ -37,6 +37,8 @@
 #include "../../include/nbody_hip.h"
 #include "nbx_ctx.h"
 #include "leaf_plan.h"
+#include "leaf_law.h"
+#include "leaf_far.h"
 #include "leaf_plan_device.h"
 
 #include <cmath>
@@ -64,15 +66,7 @@ constexpr int kPadPairs = 16;                  // massless pairs behind the tile
 constexpr int kMaxOps = 64;                    // copy ops held in LDS at a time (longer lists go in chunks)
 constexpr unsigned kFlushTerms = 248;          // fp32 terms per lane between flushes into the fp64 sums (+ 2 for a closing single pair)
 
-// smallest fp32 thresholds that are >= the reference's fp64 ones, so (r2 < T_f32) == ((double)r2 < T) for fp32 r2
-constexpr float kTreeSkipF = 0x1.12e0c0p-30f;   // 1.00000008e-9  (octree.cpp:119, bvh.cpp:167: dist_sq < 1e-9)
-constexpr float kSmoothF = 0x1.b7cdfep-34f;     // 1.00000001e-10 (fmm_parlay.cpp:1010: dist_sq < 1e-10)
-constexpr float kNormZeroF = 0x1.79ca12p-67f;   // 1.00000005e-20 (vector.h:93-97: |diff| < 1e-10 -> zero vector)
-constexpr float kSameF = 1.0e-14f;              // largest fp32 <= 1e-14 (fmm_parlay.cpp:995-1000: |d_k| > 1e-14 -> distinct)
-static_assert((double)kTreeSkipF >= 1e-9 && (double)kSmoothF >= 1e-10 && (double)kNormZeroF >= 1e-20 && (double)kSameF <= 1e-14,
-              "fp32 thresholds must sit on the right side of the fp64 ones");
-constexpr float kFar = 1.0e18f;                 // pad bodies: massless, r^2 ~ 1e36 is finite in fp32 and the weight underflows to 0
-static_assert(kTreeSkipF < 9.0e-7f, "a target outside the close set (nbx_internal.h) has no non-zero r^2 below 9.5e-7: no law's special case can apply to it");
+// the laws' thresholds, kFar and leaf_weight: leaf_law.h (shared with the far-field pass, leaf_far_kernel.hip)
 
 struct LeafArgs {
     const float4* __restrict__ xp;     // [pslots] units: pair p = units 2p {xa,xb,ya,yb} and 2p+1 {za,zb,ma,mb}
@@ -82,31 +76,6 @@ struct LeafArgs {
     double* __restrict__ acc;          // [dim][pslots]
     const uint32_t* __restrict__ max_mass_bits;   // bit pattern of the largest |mass| as fp32 (leaf_gather_kernel); a NaN compares above every number
 };
-
-// Weight of d = p_j - p_i in the law's sum for ONE pair, every special case included: m_j / r^4 for an ordinary pair.
-template <int D, int LAW>
-__device__ __forceinline__ float leaf_weight(float r2, float mj, float dx, float dy, float dz) {
-    if (LAW == NBX_LAW_BRUTE) {
-        const float g = (r2 < kR2SkipF) ? __builtin_inff() : r2;           // methods.cpp:24
-        const float ri = __builtin_amdgcn_rcpf(g);
-        return mj * ri * ri;
-    } else if (LAW == NBX_LAW_TREE_LEAF) {
-        // "same position" (every |d_k| <= 1e-9) implies r2 <= 3e-18 < 1e-9: one test covers both skips
-        const float g = (r2 < kTreeSkipF) ? __builtin_inff() : r2;
-        const float ri = __builtin_amdgcn_rcpf(g);
-        return mj * ri * ri;
-    } else {
-        if (r2 < kSmoothF) {   // rare: smoothed magnitude, unsmoothed direction (fmm_parlay.cpp:1010-1020, vector.h:93-97)
-            const bool same = __builtin_fabsf(dx) <= kSameF && __builtin_fabsf(dy) <= kSameF && (D == 2 || __builtin_fabsf(dz) <= kSameF);
-            const float r2s = r2 + 1.0e-10f;                                                   // epsilon^2, epsilon = 1e-5
-            const float mag = mj * __builtin_amdgcn_rcpf(r2s) * __builtin_amdgcn_rsqf(r2s);    // m / (r2s * sqrt(r2s))
-            const float inv = (r2 < kNormZeroF) ? 0.0f : __builtin_amdgcn_rsqf(r2);               // normalized(): 0 below 1e-10
-            return same ? 0.0f : mag * inv;
-        }
-        const float ri = __builtin_amdgcn_rcpf(r2);
-        return mj * ri * ri;
-    }
-}
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -908,6 +877,19 @@ struct nbx_leaf_plan {
     char* raw_arena = nullptr;      // one-shot call: the staged bodies come from the parked pool instead of hipMalloc
     size_t raw_arena_bytes = 0;
     nbx_leaf_dev::Summary summary_host;   // the device planner's 64 bytes land here
+    // ---- the far field (nbx_leaf_plan_set_cells; leaf_far.h): cells, far lists and the moments of the last evaluation ----
+    size_t n_leaves = 0;
+    uint32_t* unit_off = nullptr;   // [n_leaves + 1] first padded slot of every leaf (in the arena; either planner leaves it there)
+    std::vector<uint32_t> unit_host;   // the host planner's copy of it (empty after the device planner: set_cells then reads it back)
+    nbx_far::FarDevice far;         // n_cells = 0: no far field, and nothing below is touched by an evaluation
+    size_t far_entries = 0;
+    char* cell_arena = nullptr;     // every array `far` names that is the cells' own
+    size_t cell_arena_bytes = 0;
+    hipEvent_t evm0 = nullptr, evm1 = nullptr, evf0 = nullptr, evf1 = nullptr;   // moment pass, far pass (created with the first cells)
+    // an evaluation has run since the cells were set: only then do cell_rec / cell_mass hold moments.  plan_release_cells (every
+    // set_cells, destroy) clears it; nbx_leaf_plan_get_cells and the far pass of nbx_leaf_plan_time_kernel rely on that.
+    bool cells_evaluated = false;
+    bool cells_timed = false;       // ... and it recorded the four events
 };
 
 namespace {
@@ -1149,7 +1131,8 @@ int plan_mark_done(nbx_leaf_plan* p, hipStream_t s) {
     return NBX_OK;
 }
 
-int plan_launch_pairs(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
+// the near field: the pair kernels, which WRITE the slot-ordered sums
+int plan_launch_near(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
     if (p->n_blocks == 0 && p->n_packs == 0) return NBX_OK;
     if (timed) NBX_HIP_TRY(hipEventRecord(p->ev0, s));
     LeafArgs a;
@@ -1171,6 +1154,29 @@ int plan_launch_pairs(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
     }
     if (timed) NBX_HIP_TRY(hipEventRecord(p->ev1, s));
     return NBX_OK;
+}
+
+// The far field (leaf_far_kernel.hip): the far terms of the plan's cells ADDED to the sums the pair kernels wrote.
+int plan_launch_far(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
+    if (!p->far.n_cells) return NBX_OK;
+    if (timed) NBX_HIP_TRY(hipEventRecord(p->evf0, s));
+    NBX_HIP_TRY(nbx_far::enqueue_far(p->far, p->dim, law, s));
+    if (timed) NBX_HIP_TRY(hipEventRecord(p->evf1, s));
+    p->cells_evaluated = true;
+    p->cells_timed = timed;
+    return NBX_OK;
+}
+
+// One evaluation's kernels behind the gather: the cells' moments from the positions just gathered, the near field, the far field.
+// A plan without cells launches the pair kernels and nothing else.
+int plan_launch_pairs(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
+    if (p->far.n_cells) {
+        if (timed) NBX_HIP_TRY(hipEventRecord(p->evm0, s));
+        NBX_HIP_TRY(nbx_far::enqueue_moments(p->far, p->dim, s));
+        if (timed) NBX_HIP_TRY(hipEventRecord(p->evm1, s));
+    }
+    if (int rc = plan_launch_near(p, law, s, timed)) return rc;
+    return plan_launch_far(p, law, s, timed);
 }
 
 int plan_forces_out(nbx_leaf_plan* p, hipStream_t s, double* forces_out) {
@@ -1207,6 +1213,7 @@ int create_plan_on_device(nbx_leaf_plan* p, const uint32_t* leaf_offsets, const 
     const DevicePlan d = plan_pointers(p->arena, L);
     p->xp = d.xp; p->sums = d.sums; p->pslot_body = d.pslot_body; p->body_slot = d.body_slot; p->ops = d.ops; p->blocks = d.blocks;
     p->subs = d.subs; p->packs = d.packs; p->max_mass = d.max_mass;
+    p->unit_off = reinterpret_cast<uint32_t*>(p->arena + L.unit_off);
     if (forces_bytes) { p->forces = reinterpret_cast<double*>(p->arena + forces_off); p->forces_in_arena = true; }
     PLAN_TRY(enqueue_device_plan(b, p->dim, leaf_offsets, leaf_bodies, list_offsets, list_sources, NBX_LEAF_PACK != 0, p->arena, L, p->stream, &p->summary_host));
     PLAN_TRY(hipStreamSynchronize(p->stream));
@@ -1234,11 +1241,11 @@ int create_plan_on_host(nbx_leaf_plan* p, const uint32_t* leaf_offsets, const ui
     try { body_slot.assign(n, 0xffffffffu); } catch (...) { nbx_leaf_plan_destroy(p); return fail(NBX_ERR_ALLOC, "host allocation failed"); }
     for (size_t s = 0; s < p->pslots; ++s)
         if (host.pslot_body[s] != 0xffffffffu) body_slot[host.pslot_body[s]] = (uint32_t)s;
-    const size_t sizes[10] = {(p->pslots + 2) * sizeof(float4), (size_t)dim * p->pslots * sizeof(double), p->pslots * sizeof(uint32_t),
+    const size_t sizes[11] = {(p->pslots + 2) * sizeof(float4), (size_t)dim * p->pslots * sizeof(double), p->pslots * sizeof(uint32_t),
                               n * sizeof(uint32_t), p->n_ops * sizeof(CopyOp), p->n_blocks * sizeof(LeafBlock), sizeof(uint32_t),
-                              p->n_subs * sizeof(PackSub), p->n_packs * sizeof(PackBlock), forces_bytes};
-    size_t offs[10], total = 0;
-    for (int i = 0; i < 10; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
+                              p->n_subs * sizeof(PackSub), p->n_packs * sizeof(PackBlock), forces_bytes, host.unit_off.size() * sizeof(uint32_t)};
+    size_t offs[11], total = 0;
+    for (int i = 0; i < 11; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
     PLAN_TRY(take_arena(p->device, total, &p->arena, &p->arena_bytes));   // a tree code makes a plan per step: the last plan's block, parked by its destroy
     p->xp = reinterpret_cast<float4*>(p->arena + offs[0]);
     p->sums = reinterpret_cast<double*>(p->arena + offs[1]);
@@ -1250,6 +1257,8 @@ int create_plan_on_host(nbx_leaf_plan* p, const uint32_t* leaf_offsets, const ui
     p->subs = reinterpret_cast<PackSub*>(p->arena + offs[7]);
     p->packs = reinterpret_cast<PackBlock*>(p->arena + offs[8]);
     if (forces_bytes) { p->forces = reinterpret_cast<double*>(p->arena + offs[9]); p->forces_in_arena = true; }
+    p->unit_off = reinterpret_cast<uint32_t*>(p->arena + offs[10]);   // the far field's passes walk the leaves' slots by it (leaf_far.h)
+    if (sizes[10]) PLAN_TRY(hipMemcpyAsync(p->unit_off, host.unit_off.data(), sizes[10], hipMemcpyHostToDevice, p->stream));
     if (p->n_packs) {
         PLAN_TRY(hipMemcpyAsync(p->subs, host.pack_subs.data(), sizes[7], hipMemcpyHostToDevice, p->stream));
         PLAN_TRY(hipMemcpyAsync(p->packs, host.pack_blocks.data(), sizes[8], hipMemcpyHostToDevice, p->stream));
@@ -1259,6 +1268,7 @@ int create_plan_on_host(nbx_leaf_plan* p, const uint32_t* leaf_offsets, const ui
     if (p->n_ops) PLAN_TRY(hipMemcpyAsync(p->ops, host.ops.data(), sizes[4], hipMemcpyHostToDevice, p->stream));
     if (p->n_blocks) PLAN_TRY(hipMemcpyAsync(p->blocks, host.blocks.data(), sizes[5], hipMemcpyHostToDevice, p->stream));
     PLAN_TRY(hipStreamSynchronize(p->stream));   // the host arrays above go out of scope
+    p->unit_host.swap(host.unit_off);
     return NBX_OK;
 }
 
@@ -1279,7 +1289,7 @@ int create_plan(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32
     if (device < 0 || device >= ndev) return fail(NBX_ERR_NO_DEVICE, "device ordinal out of range");
     nbx_leaf_plan* p = new (std::nothrow) nbx_leaf_plan();
     if (!p) return fail(NBX_ERR_ALLOC, "host allocation failed");
-    p->device = device; p->dim = dim; p->n = n;
+    p->device = device; p->dim = dim; p->n = n; p->n_leaves = n_leaves;
     DeviceScope scope;
     PLAN_TRY(hipSetDevice(device));
     PLAN_TRY(nbx::take_stream(device, &p->stream));
@@ -1306,6 +1316,29 @@ int create_plan(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32
 
 }  // namespace
 
+namespace {
+// Gives the cells' device arrays back (parked when nothing on the device can still touch them) and forgets the cells; with
+// `events` the four timing events go too (destroy).
+void plan_release_cells(nbx_leaf_plan* p, bool device_idle, bool events) {
+    if (p->cell_arena) {
+        if (device_idle) park_arena(p->device, p->cell_arena, p->cell_arena_bytes);
+        else (void)hipFree(p->cell_arena);
+    }
+    p->cell_arena = nullptr;
+    p->cell_arena_bytes = 0;
+    p->far = nbx_far::FarDevice();
+    p->far_entries = 0;
+    p->cells_evaluated = p->cells_timed = false;
+    if (events) {
+        hipEvent_t* const evs[4] = {&p->evm0, &p->evm1, &p->evf0, &p->evf1};
+        for (hipEvent_t* e : evs) {
+            if (*e) (void)hipEventDestroy(*e);
+            *e = nullptr;
+        }
+    }
+}
+}  // namespace
+
 extern "C" {
 
 int nbx_leaf_plan_create(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies,
@@ -1321,6 +1354,7 @@ int nbx_leaf_plan_destroy(nbx_leaf_plan* p) {
     // wait on the plan's own event, which every piece of work queued on a foreign stream is followed by
     p->last_wait_ok = !(p->last_stream && p->done) || hipEventSynchronize(p->done) == hipSuccess;
     bool idle = p->stream && hipStreamSynchronize(p->stream) == hipSuccess;
+    plan_release_cells(p, idle && p->last_wait_ok, true);
     if (p->arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->arena, p->arena_bytes); else (void)hipFree(p->arena); }
     if (p->forces && !p->forces_in_arena) (void)hipFree(p->forces);
     if (p->raw_arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->raw_arena, p->raw_arena_bytes); else (void)hipFree(p->raw_arena); }
@@ -1488,6 +1522,108 @@ int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double d
     return plan_mark_done(p, s);
 }
 
+int nbx_leaf_plan_set_cells(nbx_leaf_plan* p, const uint32_t* cell_first_leaf, const uint32_t* cell_leaf_count, size_t n_cells,
+                            const uint32_t* far_offsets, const uint32_t* far_cells) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    // every index the two passes will follow, before anything is launched; a refused call leaves the plan and its cells as they were
+    if (const char* why = nbx_far::validate_cells(p->n_leaves, cell_first_leaf, cell_leaf_count, n_cells, far_offsets, far_cells))
+        return fail(NBX_ERR_INVALID, why);
+    DeviceScope scope;
+    int rc = plan_set_device(p);
+    if (rc) return rc;
+    hipStream_t s = p->stream;   // the plan's own stream, behind the last evaluation wherever that was queued
+    if ((rc = plan_order_after_last(p, s))) return rc;
+    if (!n_cells) {
+        NBX_HIP_TRY(hipStreamSynchronize(s));
+        plan_release_cells(p, true, false);
+        return plan_mark_done(p, s);
+    }
+    nbx_far::FarPlan fp;
+    std::vector<uint32_t> read_back;
+    const uint32_t* unit = p->unit_host.data();
+    if (p->unit_host.size() != p->n_leaves + 1) {      // laid out on the device: the array comes back once per set_cells (4 B per leaf)
+        try { read_back.assign(p->n_leaves + 1, 0u); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
+        if (p->n_leaves) {
+            NBX_HIP_TRY(hipMemcpyAsync(read_back.data(), p->unit_off, (p->n_leaves + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            NBX_HIP_TRY(hipStreamSynchronize(s));
+        }
+        unit = read_back.data();
+    }
+    try { nbx_far::plan_far(unit, p->n_leaves, cell_leaf_count, n_cells, far_offsets, fp); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
+    const size_t dim = (size_t)p->dim;
+    const size_t sizes[10] = {n_cells * 4, n_cells * 4, fp.small_cells.size() * 4, fp.big_cells.size() * 4, fp.far_entries * 4,
+                              fp.blocks.size() * sizeof(nbx_far::FarBlock), p->n_leaves * 4 * sizeof(double), n_cells * sizeof(double),
+                              n_cells * dim * sizeof(double), n_cells * sizeof(float4)};
+    size_t offs[10], total = 0;
+    for (int i = 0; i < 10; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
+    char* arena = nullptr;
+    size_t arena_bytes = 0;
+    NBX_HIP_TRY(take_arena(p->device, total, &arena, &arena_bytes));
+    hipError_t e = hipSuccess;
+    for (hipEvent_t* ev : {&p->evm0, &p->evm1, &p->evf0, &p->evf1})
+        if (!*ev && e == hipSuccess) e = hipEventCreate(ev);
+    const void* const src[6] = {cell_first_leaf, cell_leaf_count, fp.small_cells.data(), fp.big_cells.data(), far_cells, fp.blocks.data()};
+    for (int i = 0; i < 6 && e == hipSuccess; ++i)
+        if (sizes[i]) e = hipMemcpyAsync(arena + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // the caller's arrays and the layout's are copied; the last evaluation is over too
+    if (e != hipSuccess) {
+        (void)hipFree(arena);
+        return nbx::fail_hip(e, "uploading the cells", __FILE__, __LINE__);
+    }
+    plan_release_cells(p, true, false);                 // the previous cells, if any: nothing on the device uses them any more
+    p->cell_arena = arena;
+    p->cell_arena_bytes = arena_bytes;
+    nbx_far::FarDevice& d = p->far;
+    d.xp = p->xp; d.unit_off = p->unit_off; d.sums = p->sums;
+    d.pslots = (uint32_t)p->pslots; d.n_leaves = (uint32_t)p->n_leaves; d.n_cells = (uint32_t)n_cells;
+    d.n_small = (uint32_t)fp.small_cells.size(); d.n_big = (uint32_t)fp.big_cells.size(); d.n_blocks = (uint32_t)fp.blocks.size();
+    d.cell_first = reinterpret_cast<uint32_t*>(arena + offs[0]);
+    d.cell_count = reinterpret_cast<uint32_t*>(arena + offs[1]);
+    d.small_cells = reinterpret_cast<uint32_t*>(arena + offs[2]);
+    d.big_cells = reinterpret_cast<uint32_t*>(arena + offs[3]);
+    d.far_cells = reinterpret_cast<uint32_t*>(arena + offs[4]);
+    d.blocks = reinterpret_cast<nbx_far::FarBlock*>(arena + offs[5]);
+    d.leaf_mom = reinterpret_cast<double*>(arena + offs[6]);
+    d.cell_mass = reinterpret_cast<double*>(arena + offs[7]);
+    d.cell_com = reinterpret_cast<double*>(arena + offs[8]);
+    d.cell_rec = reinterpret_cast<float4*>(arena + offs[9]);
+    p->far_entries = fp.far_entries;
+    return plan_mark_done(p, s);
+}
+
+int nbx_leaf_plan_get_cells(nbx_leaf_plan* p, double* mass_out, double* com_out) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (!p->far.n_cells) return NBX_OK;
+    if (!p->cells_evaluated) return fail(NBX_ERR_STATE, "no evaluation since the cells were set");
+    DeviceScope scope;
+    int rc = plan_set_device(p);
+    if (rc) return rc;
+    hipStream_t s = p->stream;
+    if ((rc = plan_order_after_last(p, s))) return rc;
+    const size_t nc = p->far.n_cells;
+    if (mass_out) NBX_HIP_TRY(hipMemcpyAsync(mass_out, p->far.cell_mass, nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (com_out) NBX_HIP_TRY(hipMemcpyAsync(com_out, p->far.cell_com, nc * (size_t)p->dim * sizeof(double), hipMemcpyDeviceToHost, s));
+    NBX_HIP_TRY(hipStreamSynchronize(s));
+    return plan_mark_done(p, s);
+}
+
+int nbx_leaf_plan_cell_info(nbx_leaf_plan* p, size_t* n_cells, size_t* far_entries, float* moments_ms, float* far_ms) {
+    if (moments_ms) *moments_ms = 0.0f;
+    if (far_ms) *far_ms = 0.0f;
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (n_cells) *n_cells = p->far.n_cells;
+    if (far_entries) *far_entries = p->far_entries;
+    if ((moments_ms || far_ms) && p->far.n_cells && p->cells_evaluated && p->cells_timed) {
+        DeviceScope scope;
+        int rc = plan_set_device(p);
+        if (rc) return rc;
+        NBX_HIP_TRY(hipEventSynchronize(p->evf1));
+        if (moments_ms) NBX_HIP_TRY(hipEventElapsedTime(moments_ms, p->evm0, p->evm1));
+        if (far_ms) NBX_HIP_TRY(hipEventElapsedTime(far_ms, p->evf0, p->evf1));
+    }
+    return NBX_OK;
+}
+
 int nbx_leaf_plan_time_kernel(nbx_leaf_plan* p, int law, int reps, float* mean_ms) {
     if (!p || !mean_ms) return fail(NBX_ERR_INVALID, "null argument");
     *mean_ms = 0.0f;
@@ -1502,9 +1638,10 @@ int nbx_leaf_plan_time_kernel(nbx_leaf_plan* p, int law, int reps, float* mean_m
     const int timed_from = reps / 2;
     for (int r = 0; r < reps; ++r) {
         if (r == timed_from) NBX_HIP_TRY(hipEventRecord(p->ev0, s));
-        if ((rc = plan_launch_pairs(p, law, s, false))) return rc;
+        if ((rc = plan_launch_near(p, law, s, false))) return rc;
     }
     NBX_HIP_TRY(hipEventRecord(p->ev1, s));
+    if (p->cells_evaluated && (rc = plan_launch_far(p, law, s, false))) return rc;   // the sums keep their far terms (the last evaluation's moments)
     NBX_HIP_TRY(hipStreamSynchronize(s));
     if (p->n_blocks || p->n_packs) NBX_HIP_TRY(hipEventElapsedTime(mean_ms, p->ev0, p->ev1));
     *mean_ms /= (float)(reps - timed_from);

@@ -57,6 +57,14 @@ LeafPairSimulationHip<D>::LeafPairSimulationHip(const std::vector<Body<D>>& bodi
     const int device = leaf_device();
     int rc = nbx_leaf_plan_create(&plan_, device, D, n_, L.leaf_offsets.data(), L.leaf_bodies.data(), L.leaves(), L.list_offsets.data(),
                                   L.list_sources.data());
+    if (!rc && L.cells()) {
+        if (L.cell_leaf_count.size() != L.cells() || L.far_offsets.size() != L.leaf_offsets.size()) {
+            nbx_leaf_plan_destroy(plan_);
+            plan_ = nullptr;
+            throw std::runtime_error("LeafPairSimulationHip: cell_leaf_count needs n_cells entries and far_offsets n_leaves + 1");
+        }
+        rc = nbx_leaf_plan_set_cells(plan_, L.cell_first_leaf.data(), L.cell_leaf_count.data(), L.cells(), L.far_offsets.data(), L.far_cells.data());
+    }
     if (!rc) rc = nbx_ctx_create(&ctx_, device, D, n_, 1, 0);
     if (!rc) rc = nbx_ctx_upload_bodies(ctx_, bodies.data(), sizeof(Body<D>));
     if (rc != NBX_OK) {
@@ -173,6 +181,95 @@ LeafLists build_uniform_leaves(const std::vector<Body<D>>& bodies, int depth) {
     return L;
 }
 
+template <int D>
+LeafLists build_octree_cells(const std::vector<Body<D>>& bodies, int depth, double theta) {
+    LeafLists L;
+    L.far_offsets.assign(1, 0u);
+    const std::size_t n = bodies.size();
+    if (n == 0) return L;
+    const long long g = 1LL << depth;
+    Vector<D> lo = bodies[0].position, hi = bodies[0].position;
+    for (const auto& b : bodies)
+        for (int d = 0; d < D; ++d) { lo[d] = std::min(lo[d], b.position[d]); hi[d] = std::max(hi[d], b.position[d]); }
+    double half = 0.0;
+    Vector<D> centre;
+    for (int d = 0; d < D; ++d) { centre[d] = (lo[d] + hi[d]) / 2.0; half = std::max(half, (hi[d] - lo[d]) / 2.0); }
+    half = std::max(half * 1.01, 1e-300);
+    // Morton key: bit b of axis d at bit b * D + (D - 1 - d)
+    std::vector<long long> key(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        long long k = 0;
+        for (int d = 0; d < D; ++d) {
+            long long c = (long long)std::floor((bodies[i].position[d] - (centre[d] - half)) / (2.0 * half) * (double)g);
+            c = std::min(std::max(c, 0LL), g - 1);
+            for (int bit = 0; bit < depth; ++bit) k |= ((c >> bit) & 1LL) << (bit * D + (D - 1 - d));
+        }
+        key[i] = k;
+    }
+    std::vector<std::uint32_t> order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](std::uint32_t a, std::uint32_t b) { return key[a] < key[b]; });
+    L.leaf_bodies = order;
+    L.leaf_offsets.clear();
+    std::vector<long long> leaf_key;
+    for (std::size_t s = 0; s < n; ++s)
+        if (s == 0 || key[order[s]] != key[order[s - 1]]) { leaf_key.push_back(key[order[s]]); L.leaf_offsets.push_back((std::uint32_t)s); }
+    L.leaf_offsets.push_back((std::uint32_t)n);
+    const std::size_t nl = leaf_key.size();
+    // the non-empty nodes of levels 1 .. depth: keys (sorted), leaf ranges, the id of the level's first cell
+    std::vector<std::vector<long long>> lv_key(depth + 1);
+    std::vector<std::size_t> lv_base(depth + 2, 0);
+    for (int lv = 1; lv <= depth; ++lv) {
+        lv_base[lv] = L.cell_first_leaf.size();
+        for (std::size_t l = 0; l < nl; ++l) {
+            const long long k = leaf_key[l] >> (D * (depth - lv));
+            if (lv_key[lv].empty() || lv_key[lv].back() != k) { lv_key[lv].push_back(k); L.cell_first_leaf.push_back((std::uint32_t)l); L.cell_leaf_count.push_back(0u); }
+            ++L.cell_leaf_count.back();
+        }
+    }
+    auto coords = [&](long long k, int lv, long long* c) {
+        for (int d = 0; d < D; ++d) {
+            c[d] = 0;
+            for (int bit = 0; bit < lv; ++bit) c[d] |= ((k >> (bit * D + (D - 1 - d))) & 1LL) << bit;
+        }
+    };
+    L.list_offsets.assign(1, 0u);
+    std::vector<std::size_t> frontier, next;
+    for (std::size_t t = 0; t < nl; ++t) {
+        if (depth == 0) { L.list_sources.push_back((std::uint32_t)t); L.list_offsets.push_back((std::uint32_t)L.list_sources.size()); L.far_offsets.push_back(0u); continue; }
+        long long q[3];
+        coords(leaf_key[t], depth, q);
+        frontier.resize(lv_key[1].size());
+        std::iota(frontier.begin(), frontier.end(), (std::size_t)0);
+        L.list_sources.push_back((std::uint32_t)t);                       // the leaf itself first
+        for (int lv = 1; lv <= depth; ++lv) {
+            const int s = depth - lv;
+            next.clear();
+            for (const std::size_t node : frontier) {
+                long long c[3], gap2 = 0;
+                coords(lv_key[lv][node], lv, c);
+                for (int d = 0; d < D; ++d) {
+                    const long long blo = c[d] << s;
+                    const long long gd = std::max(0LL, std::max(blo - (q[d] + 1), q[d] - (blo + (1LL << s))));
+                    gap2 += gd * gd;
+                }
+                if ((double)(1LL << s) < theta * std::sqrt((double)gap2)) { L.far_cells.push_back((std::uint32_t)(lv_base[lv] + node)); continue; }
+                if (lv == depth) { if (node != t) L.list_sources.push_back((std::uint32_t)node); continue; }
+                const auto& kids = lv_key[lv + 1];
+                const std::size_t k0 = (std::size_t)(std::lower_bound(kids.begin(), kids.end(), lv_key[lv][node] << D) - kids.begin());
+                const std::size_t k1 = (std::size_t)(std::lower_bound(kids.begin(), kids.end(), (lv_key[lv][node] + 1) << D) - kids.begin());
+                for (std::size_t k = k0; k < k1; ++k) next.push_back(k);
+            }
+            frontier.swap(next);
+        }
+        L.list_offsets.push_back((std::uint32_t)L.list_sources.size());
+        L.far_offsets.push_back((std::uint32_t)L.far_cells.size());
+    }
+    return L;
+}
+
+template LeafLists build_octree_cells<2>(const std::vector<Body<2>>&, int, double);
+template LeafLists build_octree_cells<3>(const std::vector<Body<3>>&, int, double);
 template std::vector<Vector<2>> leaf_pair_direct_forces_hip<2>(const std::vector<Body<2>>&, const LeafLists&, LeafLaw);
 template std::vector<Vector<3>> leaf_pair_direct_forces_hip<3>(const std::vector<Body<3>>&, const LeafLists&, LeafLaw);
 template LeafLists build_uniform_leaves<2>(const std::vector<Body<2>>&, int);

@@ -17,9 +17,14 @@
 
 // leaf l owns bodies leaf_bodies[leaf_offsets[l] .. leaf_offsets[l+1]); target leaf t sums over the source leaves
 // list_sources[list_offsets[t] .. list_offsets[t+1]) (own leaf included explicitly, fmm_parlay.cpp:973-974).
+// The far field (optional; nbx_leaf_plan_set_cells): cell c is the leaves [cell_first_leaf[c], cell_first_leaf[c] + cell_leaf_count[c]);
+// target leaf t is attracted by the cells far_cells[far_offsets[t] .. far_offsets[t+1]) as by one pseudo-body each (total mass at
+// the centre of mass: octree.cpp:129-151, bvh.cpp:203-239).  Empty cell arrays: no far field.
 struct LeafLists {
     std::vector<std::uint32_t> leaf_offsets{0}, leaf_bodies, list_offsets{0}, list_sources;
+    std::vector<std::uint32_t> cell_first_leaf, cell_leaf_count, far_offsets, far_cells;
     std::size_t leaves() const { return leaf_offsets.size() - 1; }
+    std::size_t cells() const { return cell_first_leaf.size(); }
 };
 
 enum class LeafLaw : int {
@@ -35,7 +40,7 @@ std::vector<Vector<D>> leaf_pair_direct_forces_hip(const std::vector<Body<D>>& b
 
 // The same sums for a tree that STANDS while the bodies move -- the reference's call pattern: bvh.cpp:143-176 evaluates the
 // leaf sums of a built BVH in every force evaluation, fmm_parlay.cpp:916-1022 once per step.  The structure is validated, laid
-// out and uploaded once (nbx_leaf_plan_*), the bodies live on the device (a context), and every evaluation only re-gathers
+// out and uploaded once (nbx_leaf_plan_*; with the lists' cells and far lists, if any: every evaluation then carries near + far), the bodies live on the device (a context), and every evaluation only re-gathers
 // positions and runs the pair kernel.  Every method throws std::runtime_error on failure; no CPU fallback.
 template <int D>
 class LeafPairSimulationHip {
@@ -65,6 +70,13 @@ private:
 // tree that produces the reference's neighbour-list structure (fmm.cpp:455-476).
 template <int D>
 LeafLists build_uniform_leaves(const std::vector<Body<D>>& bodies, int depth);
+
+// A fixed-depth octree (quadtree for D = 2) with near AND far lists, the twin of nbody_amd.leaves.octree_cells: leaves = the non-empty
+// cells of the 2^depth grid in MORTON order (every node is a contiguous range of leaves), cells = the non-empty nodes of levels
+// 1 .. depth, and per target leaf a top-down walk that sends a node to the far list when side(node) < theta * gap (gap: box-to-box
+// distance between the leaf's grid box and the node's) and a leaf-level node that is not accepted to the near list, the leaf first.
+template <int D>
+LeafLists build_octree_cells(const std::vector<Body<D>>& bodies, int depth, double theta);
 
 // kernel time of the most recent leaf_pair_direct_forces_hip call on this thread (ms)
 float last_leaf_pair_kernel_ms();

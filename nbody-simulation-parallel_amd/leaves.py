@@ -142,3 +142,102 @@ def median_split_leaves(bodies: np.ndarray, dim: int, max_leaf_size: int = 16, r
     rank = np.arange(rows.size) - np.repeat(np.cumsum(counts) - counts, counts)
     list_sources[list_offsets[rows] + 1 + rank] = c
     return (leaf_offsets, order.astype(np.uint32), np.asarray(list_offsets, dtype=np.uint32), np.asarray(list_sources, dtype=np.uint32))
+
+
+def _morton_keys(cell: np.ndarray, dim: int, depth: int) -> np.ndarray:
+    """Morton (Z-order) key of integer cell coordinates: bit b of axis d lands at bit b * dim + (dim - 1 - d)."""
+    key = np.zeros(cell.shape[0], dtype=np.int64)
+    for bit in range(depth):
+        for d in range(dim):
+            key |= ((cell[:, d] >> bit) & 1) << (bit * dim + (dim - 1 - d))
+    return key
+
+
+def _morton_coords(keys: np.ndarray, dim: int, level: int) -> np.ndarray:
+    out = np.zeros((keys.size, dim), dtype=np.int64)
+    for bit in range(level):
+        for d in range(dim):
+            out[:, d] |= ((keys >> (bit * dim + (dim - 1 - d))) & 1) << bit
+    return out
+
+
+def octree_cells(bodies: np.ndarray, dim: int, depth: int, theta: float, chunk_leaves: int = 16384):
+    """A fixed-depth octree (quadtree in 2D) with near AND far lists, for nbx_leaf_plan_set_cells.  Returns
+    (leaf_offsets, leaf_bodies, list_offsets, list_sources, cell_first_leaf, cell_leaf_count, far_offsets, far_cells), all uint32.
+    Leaves: the non-empty cells of the 2^depth grid over the 1 %-padded bounding box (as uniform_grid_leaves), in MORTON order, so
+    that every node of the tree is a contiguous range of leaves.  Cells: the non-empty nodes of levels 1 .. depth, level by level
+    (the last `n_leaves` cells are the leaves themselves).  Per target leaf a top-down walk (octree.cpp:129-151's acceptance
+    test on boxes): a node goes to the far list when side(node) < theta * gap, gap = the box-to-box distance between the leaf's
+    grid box and the node's grid box -- so every body of an accepted node is farther than side / theta from every body of the
+    leaf; a leaf-level node that is not accepted goes to the near list, the leaf itself first.  theta = 0 accepts nothing.
+    The walk is level-synchronous over a frontier of (leaf, node) pairs, `chunk_leaves` target leaves at a time (memory)."""
+    pos = np.asarray(bodies)[:, :dim]
+    n = pos.shape[0]
+    u32 = lambda a: np.asarray(a, dtype=np.uint32)
+    none = np.zeros(0, dtype=np.uint32)
+    if n == 0:
+        z = np.zeros(1, dtype=np.uint32)
+        return z, none, z.copy(), none.copy(), none.copy(), none.copy(), z.copy(), none.copy()
+    g = 1 << depth
+    lo, hi = pos.min(axis=0), pos.max(axis=0)
+    centre, half = (lo + hi) / 2.0, max(float((hi - lo).max()) / 2.0 * 1.01, 1e-300)
+    cell = np.clip(np.floor((pos - (centre - half)) / (2.0 * half) * g).astype(np.int64), 0, g - 1)
+    key = _morton_keys(cell, dim, depth)
+    order = np.argsort(key, kind="stable")
+    keys, first = np.unique(key[order], return_index=True)
+    nl = keys.size
+    leaf_offsets = np.append(first, n)
+    # the non-empty nodes of every level: keys (sorted), leaf ranges, coordinates, children (a contiguous range of the next level)
+    lv_keys, lv_first, lv_count, lv_coords, lv_base = {}, {}, {}, {}, {}
+    base = 0
+    for L in range(1, depth + 1):
+        kl, f, c = np.unique(keys >> (dim * (depth - L)), return_index=True, return_counts=True)
+        lv_keys[L], lv_first[L], lv_count[L], lv_coords[L], lv_base[L] = kl, f, c, _morton_coords(kl, dim, L), base
+        base += kl.size
+    child_first, child_count = {}, {}
+    for L in range(1, depth):
+        child_first[L] = np.searchsorted(lv_keys[L + 1], lv_keys[L] << dim)
+        child_count[L] = np.searchsorted(lv_keys[L + 1], (lv_keys[L] + 1) << dim) - child_first[L]
+    q = lv_coords[depth] if depth >= 1 else np.zeros((nl, dim), dtype=np.int64)
+    near_t, near_s, far_t, far_c = [], [], [], []
+    for t0 in range(0, nl, max(1, int(chunk_leaves))):
+        t1 = min(nl, t0 + max(1, int(chunk_leaves)))
+        if depth == 0:                                             # one leaf, no levels below the root: itself
+            near_t.append(np.arange(t0, t1)); near_s.append(np.arange(t0, t1))
+            continue
+        n1 = lv_keys[1].size
+        t = np.repeat(np.arange(t0, t1, dtype=np.int64), n1)
+        node = np.tile(np.arange(n1, dtype=np.int64), t1 - t0)
+        ft, fc = [], []
+        for L in range(1, depth + 1):
+            s = depth - L
+            blo = lv_coords[L][node] << s
+            qt = q[t]
+            gap = np.maximum(0, np.maximum(blo - (qt + 1), qt - (blo + (1 << s))))
+            acc = float(1 << s) < theta * np.sqrt((gap * gap).sum(axis=1).astype(np.float64))
+            ft.append(t[acc]); fc.append(lv_base[L] + node[acc])
+            t, node = t[~acc], node[~acc]
+            if L == depth:
+                break
+            cnt = child_count[L][node]
+            start = np.repeat(np.cumsum(cnt) - cnt, cnt)
+            kid = np.repeat(child_first[L][node], cnt) + (np.arange(int(cnt.sum()), dtype=np.int64) - start)
+            t, node = np.repeat(t, cnt), kid
+        by = np.lexsort((node, node != t, t))                      # per leaf: itself first, then the others in Morton order
+        near_t.append(t[by]); near_s.append(node[by])
+        ft, fc = np.concatenate(ft), np.concatenate(fc)
+        by = np.argsort(ft, kind="stable")                         # per leaf: coarse levels first, Morton order within a level
+        far_t.append(ft[by]); far_c.append(fc[by])
+    near_t, near_s = np.concatenate(near_t), np.concatenate(near_s)
+    list_offsets = np.concatenate([[0], np.cumsum(np.bincount(near_t, minlength=nl))])
+    if far_t:
+        far_t, far_c = np.concatenate(far_t), np.concatenate(far_c)
+    else:
+        far_t = far_c = np.zeros(0, dtype=np.int64)
+    far_offsets = np.concatenate([[0], np.cumsum(np.bincount(far_t, minlength=nl))])
+    if depth >= 1:
+        cell_first = np.concatenate([lv_first[L] for L in range(1, depth + 1)])
+        cell_count = np.concatenate([lv_count[L] for L in range(1, depth + 1)])
+    else:
+        cell_first = cell_count = none
+    return (u32(leaf_offsets), u32(order), u32(list_offsets), u32(near_s), u32(cell_first), u32(cell_count), u32(far_offsets), u32(far_c))
