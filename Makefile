@@ -18,11 +18,14 @@ all: lib oracle nbody_sim
 
 lib: $(LIB)
 
-OBJS := $(CSRC)/force_kernel.o $(CSRC)/force_launch.o \
+OBJS := $(CSRC)/force_kernel.o $(CSRC)/force_sym_kernel.o $(CSRC)/force_launch.o \
         $(CSRC)/state_kernels.o $(CSRC)/nbx_api.o $(CSRC)/nbx_node.o $(CSRC)/leaf_pair_kernel.o $(CSRC)/leaf_far_kernel.o $(CSRC)/close_hash.o $(CSRC)/measure_kernels.o
 # name of the force-kernel variant used when the caller does not pick one
 # (round 4: the three-level summation build -- same pair arithmetic, fp32 errors ~3x smaller for +1.5 % time)
 DEFAULT_VARIANT ?= fastpk3l_t8_w3_u4
+# 1: a single-shard context that was not given a variant runs the symmetric own-shard pass (sympk3l_t8_w3) where its
+# decomposition applies; 0: only on request.  The default variant's name above does not change.
+SYM_DEFAULT ?= 1
 # exact (self-contained, guarded) variant used when the fast path's preconditions do not hold
 DEFAULT_EXACT_VARIANT ?= lds_t1_w8_exact_u8
 
@@ -30,15 +33,19 @@ DEFAULT_EXACT_VARIANT ?= lds_t1_w8_exact_u8
 $(CSRC)/force_kernel.o: $(CSRC)/force_kernel.hip $(CSRC)/nbx_internal.h
 	$(HIPCC) $(HIPFLAGS) $(FORCE_KERNEL_DEFS) -fno-slp-vectorize -c $< -o $@
 
-$(CSRC)/force_launch.o: $(CSRC)/force_launch.hip $(CSRC)/nbx_internal.h Makefile
+# the symmetric own-shard pass: same flags as the one-sided force kernels
+$(CSRC)/force_sym_kernel.o: $(CSRC)/force_sym_kernel.hip $(CSRC)/sym_plan.h $(CSRC)/nbx_internal.h
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+$(CSRC)/force_launch.o: $(CSRC)/force_launch.hip $(CSRC)/nbx_internal.h $(CSRC)/sym_plan.h Makefile
 	$(HIPCC) $(HIPFLAGS) -DNBX_DEFAULT_VARIANT='"$(DEFAULT_VARIANT)"' -DNBX_DEFAULT_EXACT_VARIANT='"$(DEFAULT_EXACT_VARIANT)"' -c $< -o $@
 
 # -ffp-contract=off: the fp64 kick/drift must round like the reference's two-step arithmetic
 $(CSRC)/state_kernels.o: $(CSRC)/state_kernels.hip $(CSRC)/nbx_internal.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 
-$(CSRC)/nbx_api.o: $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(CSRC)/nbx_api.o: $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h Makefile
+	$(HIPCC) $(HIPFLAGS) -DNBX_SYM_DEFAULT=$(SYM_DEFAULT) -c $< -o $@
 
 $(CSRC)/nbx_node.o: $(CSRC)/nbx_node.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

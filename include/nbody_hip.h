@@ -388,7 +388,12 @@ int nbx_ctx_refine_stats(nbx_ctx* ctx, unsigned* selected, unsigned* refined);
  *                                sum's error: backward error = |da_i| / S_i, condition number kappa_i = S_i / |a_i|).
  * NBX_ERR_STATE after any other evaluation.  Synchronises the stream. */
 int nbx_ctx_get_aux(nbx_ctx* ctx, double* out);
-/* The variant and slice count the next force evaluation will use (after upload). */
+/* The variant and slice count the next force evaluation will use (after upload).  A single-shard context that was given
+ * neither a variant nor a slice count reports "sympk3l_t8_w3" -- the symmetric own-shard pass, every unordered pair evaluated
+ * once -- where its shard has 8 to 255 super-blocks of 8,192 bodies, and then the pass's S + K slots as the slice count
+ * (DESIGN.md section 3); nbx_default_variant() keeps naming the one-sided kernel that every other context runs.  A context
+ * that was ASKED for "sympk3l_t8_w3" where the pass does not apply (a multi-shard context, fewer than two or more than 255
+ * super-blocks) reports that name and runs the one-sided three-level kernel: the same pairs in the same arithmetic. */
 int nbx_ctx_effective_tuning(nbx_ctx* ctx, int* variant, int* source_splits);
 int nbx_num_variants(void);
 const char* nbx_variant_name(int variant);

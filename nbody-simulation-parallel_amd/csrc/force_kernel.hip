@@ -854,6 +854,14 @@ __device__ __forceinline__ void close_set_path(const KArgs& a, float4 (&tile)[2]
     }
 }
 
+// The close set in a launch of its own, grid = (kCloseBlocksX, source slices): for the symmetric pass (force_sym_kernel.hip), whose
+// workgroups are not (target block, source slice) pairs.
+template <int D>
+__global__ __launch_bounds__(256) void close_set_kernel(KArgs a) {
+    __shared__ float4 tile[2][kTile];
+    close_set_path<D>(a, tile, blockIdx.x, blockIdx.y);
+}
+
 // Fold the close-set path's slices (fp64, slice order) into acc: slice 0 receives the sum (added to
 // what a preceding LOCAL pass left there when accumulating), the other slices are zeroed.
 template <int D>
@@ -1062,6 +1070,7 @@ CloseKernels close_kernels() {
     k.classify_src[0] = classify_sources_kernel<2>; k.classify_src[1] = classify_sources_kernel<3>;
     k.refine[0] = refine_close_kernel<2>;     k.refine[1] = refine_close_kernel<3>;
     k.scatter[0] = scatter_close_kernel<2>;   k.scatter[1] = scatter_close_kernel<3>;
+    k.close_only[0] = close_set_kernel<2>;    k.close_only[1] = close_set_kernel<3>;
     k.potential[0] = potential_kernel<2, 0>;  k.potential[1] = potential_kernel<3, 0>;
     k.potential_soft[0] = potential_kernel<2, 1>; k.potential_soft[1] = potential_kernel<3, 1>;
     k.potential_newton[0] = potential_kernel<2, 2>; k.potential_newton[1] = potential_kernel<3, 2>;

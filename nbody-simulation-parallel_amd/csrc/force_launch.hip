@@ -3,6 +3,7 @@
 // and for fast variants runs the close-set pipeline (classify when positions changed -> fast kernel
 // whose extra workgroups evaluate the close set -> scatter), all asynchronous on the caller's stream with no host read-back.
 #include "nbx_internal.h"
+#include "sym_plan.h"
 
 #include <cxxabi.h>
 
@@ -23,6 +24,7 @@ struct Table {
         int n = 0;
         const KernelVariant* a = kernel_variants(&n);
         for (int i = 0; i < n; ++i) v.push_back(a[i]);
+        v.push_back(sym_kernel_variant());
         for (size_t i = 0; i < v.size(); ++i) {
             if (std::strcmp(v[i].name, NBX_DEFAULT_VARIANT) == 0) def = (int)i;
             if (std::strcmp(v[i].name, NBX_DEFAULT_EXACT_VARIANT) == 0) def_exact = (int)i;
@@ -57,6 +59,15 @@ int variant_has_law_builds(int v) { return valid(v) && table().v[v].soft2 && tab
 int variant_planes(int v) { return valid(v) ? table().v[v].planes : 1; }
 int variant_has_qsum(int v) { return valid(v) && table().v[v].qs2 && table().v[v].qs3; }
 int variant_writes_aux(int v) { return valid(v) ? table().v[v].aux : 0; }
+int variant_is_sym(int v) { return valid(v) ? table().v[v].sym : 0; }
+int variant_sym_slots(int v, unsigned pad) {
+    SymPlan P;
+    return (variant_is_sym(v) && sym_make_plan(pad, &P)) ? (int)(P.S + P.K) : 0;
+}
+int variant_sym_workgroups(int v, unsigned pad) {
+    SymPlan P;
+    return (variant_is_sym(v) && sym_make_plan(pad, &P)) ? (int)(P.B * P.S) : 0;
+}
 int variant_has_clock_stamps(int v) { return valid(v) ? table().v[v].stamps : 0; }
 int variant_kernel_symbol(int v, int dim, int law, int soft, int qsum, char* buf, size_t len) {
     if (!valid(v) || (dim != 2 && dim != 3) || !buf || len == 0) return -1;
@@ -133,6 +144,17 @@ hipError_t launch_accel(int dim, const AccelLaunch& L, hipStream_t stream) {
         return hipErrorInvalidValue;
     if (V.max_tiles_per_slice > 0 && a.tiles_per_split > (unsigned)V.max_tiles_per_slice) return hipErrorInvalidValue;
 
+    // the symmetric pass: the own chunk against itself, nothing accumulated; its S + K slots were sized by the caller from the
+    // same plan (variant_sym_slots).  The close set runs in a launch of its own over the S source slices.
+    SymPlan P = {};
+    if (V.sym) {
+        if (!sym_make_plan(L.pad, &P) || slices != P.S + P.K || L.accumulate || soft || L.law != 0 || L.vchunks != 1 ||
+            L.chunk_first != L.tgt_chunk || L.chunk_skip != INT_MAX)
+            return hipErrorInvalidValue;
+        a.grid_slices = (int)P.S;
+        a.tiles_per_split = (a.total_tiles + P.S - 1u) / P.S;
+    }
+
     a.close_blocks = (V.fast && !soft) ? (unsigned)kCloseBlocksX : 0u;
     hipError_t e = hipSuccess;
     dim3 block(256, 1, 1);
@@ -171,11 +193,16 @@ hipError_t launch_accel(int dim, const AccelLaunch& L, hipStream_t stream) {
     }
     if (L.lists_only) return hipSuccess;
     dim3 grid(L.pad / tgt_per_block + a.close_blocks, slices, 1);
+    if (V.sym) grid = dim3(P.B, P.S, 1);
     if (a.clk) {   // close-set workgroups leave their slots zero: the reader skips them
         if ((e = hipMemsetAsync(a.clk, 0, (size_t)grid.x * grid.y * 2 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
         if (L.clk_slots) *L.clk_slots = grid.x * grid.y;
     }
     if (L.ev_start && (e = hipEventRecord(L.ev_start, stream)) != hipSuccess) return e;
+    if (V.sym) {
+        hipLaunchKernelGGL(table().ck.close_only[di], dim3(a.close_blocks, P.S, 1), block, 0, stream, a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(pick_kernel(V, dim, L.law, soft, L.qsum != nullptr), grid, block, 0, stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;

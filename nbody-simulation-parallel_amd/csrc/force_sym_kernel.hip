@@ -1,0 +1,311 @@
+// force_sym_kernel.hip -- K1-S: the symmetric own-shard force pass for gfx950 (MI355X), fp32, D = 2 or 3.
+//
+// The one-sided kernels (force_kernel.hip) evaluate every ORDERED pair: d, r^2, the reciprocal and its square are computed
+// twice per pair of bodies.  This pass computes them once per UNORDERED pair and uses them for both bodies (Newton's third
+// law; per two unordered pairs 16 v_pk + 2 v_rcp for FOUR pair terms against 2 x (11 v_pk + 2 v_rcp)).  It applies where
+// the sources of a pass are exactly the context's own bodies and nothing is accumulated onto an earlier pass (a
+// single-shard context); the decomposition is in sym_plan.h.
+//
+//   * A wave holds 512 HOME bodies, 8 per lane as 4 float2 pairs with their masses, like the one-sided fast kernels.
+//   * It takes 64 VISITORS, one per lane: {x, y}, {z, m} and a float2 x 3 reaction accumulator.  One step = the fast
+//     kernel's loop body with the source operands read from the lane's visitor registers instead of an LDS broadcast, plus
+//     the multiply by the home masses and 3 v_pk_fma_f32 into the visitor's accumulator.  Then the visitor and its
+//     accumulator move one lane on (v_mov_b32_dpp wave_ror:1).  After 64 steps every home body has met every visitor and
+//     every visitor is back in its lane.  No LDS broadcast, no barrier and no cross-lane reduction in the pair loop.
+//   * Summation, three levels on both sides:
+//       home:    fp32 over the 64 steps of one visitor group -> fp32 over the <= 4 groups of a chunk -> fp64 (LDS);
+//       visitor: fp32 over 8 steps (32 terms per float2 half) -> fp32 over the 8 such blocks of a rotation, kept in the
+//                wave's LDS slot of that visitor -> fp64: the four waves of the workgroup, which meet the same visitors,
+//                are added in wave order, and the workgroup keeps the running fp64 sum over its home passes in the planes
+//                that only it writes.
+//     Q (mixed mode) adds |level-1 sum|^2 on both sides.
+//   * Deterministic: no atomics, every plane entry has one writer, every order is fixed by the indices.
+//   * kTiny bias and close set as in the fast kernels: a flagged body's home sums are not stored, and scatter_close_kernel
+//     replaces ALL its planes (the reaction slots too) by the guarded evaluation.  A pair with a flagged and an unflagged
+//     body is at r^2 >= kBadR2, so the unflagged body's term is good.
+#include "nbx_internal.h"
+#include "sym_plan.h"
+
+namespace nbx {
+namespace {
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// lane i receives lane i-1's value (lane 0: lane 63's)
+__device__ __forceinline__ float ror1(float v) {
+    const int i = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0x13C, 0xF, 0xF, false));
+}
+__device__ __forceinline__ void ror1(f2& v) { v.x = ror1(v.x); v.y = ror1(v.y); }
+
+// One step: the lane's PAIRS home pairs against the lane's visitor.  Per home pair, D = 3: v_pk_add x3, v_pk_fma x3
+// (r^2 + bias), v_rcp x2, v_pk_mul (w^2), v_pk_mul x2 (the two masses), v_pk_fma x3 (home), v_pk_fma x3 (visitor) = 16 + 2.
+// d = visitor - home: the home sums add m_v w^2 d; the visitor's accumulator adds m_h w^2 d and is NEGATED when it is flushed.
+template <int D, int PAIRS>
+__device__ __forceinline__ void sym_step(const f2 vxy, const f2 vzm, const f2 (&ix)[PAIRS], const f2 (&iy)[PAIRS],
+                                         const f2 (&iz)[PAIRS], const f2 (&hm)[PAIRS], f2 (&ax)[PAIRS], f2 (&ay)[PAIRS],
+                                         f2 (&az)[PAIRS], f2& vax, f2& vay, f2& vaz, const f2 bias) {
+    f2 dx[PAIRS], dy[PAIRS], dz[PAIRS], r2[PAIRS], w[PAIRS], wh[PAIRS];
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) dx[q] = __builtin_shufflevector(vxy, vxy, 0, 0) - ix[q];
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) dy[q] = __builtin_shufflevector(vxy, vxy, 1, 1) - iy[q];
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) dz[q] = (D == 3) ? __builtin_shufflevector(vzm, vzm, 0, 0) - iz[q] : f2{0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) r2[q] = __builtin_elementwise_fma(dx[q], dx[q], bias);
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) r2[q] = __builtin_elementwise_fma(dy[q], dy[q], r2[q]);
+    if (D == 3) {
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) r2[q] = __builtin_elementwise_fma(dz[q], dz[q], r2[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) { w[q].x = __builtin_amdgcn_rcpf(r2[q].x); w[q].y = __builtin_amdgcn_rcpf(r2[q].y); }
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) r2[q] = w[q] * w[q];
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) w[q] = __builtin_shufflevector(vzm, vzm, 1, 1) * r2[q];
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) wh[q] = hm[q] * r2[q];
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) ax[q] = __builtin_elementwise_fma(w[q], dx[q], ax[q]);
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) ay[q] = __builtin_elementwise_fma(w[q], dy[q], ay[q]);
+    if (D == 3) {
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) az[q] = __builtin_elementwise_fma(w[q], dz[q], az[q]);
+    }
+    // the three components interleaved: each accumulator is touched every third instruction
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q) {
+        vax = __builtin_elementwise_fma(wh[q], dx[q], vax);
+        vay = __builtin_elementwise_fma(wh[q], dy[q], vay);
+        if (D == 3) vaz = __builtin_elementwise_fma(wh[q], dz[q], vaz);
+    }
+}
+
+template <int D>
+__device__ __forceinline__ void load_visitor(const float* __restrict__ tp, const float* __restrict__ mp, unsigned pad,
+                                             unsigned v, f2& vxy, f2& vzm) {
+    vxy = f2{tp[v], tp[(size_t)pad + v]};
+    vzm = f2{(D == 3) ? tp[2 * (size_t)pad + v] : 0.0f, mp[v]};
+}
+
+__device__ __forceinline__ void store_hi_lo(float* __restrict__ hi_plane, float* __restrict__ lo_plane, size_t idx, double v) {
+    const float hi = (float)v;
+    hi_plane[idx] = hi;
+    lo_plane[idx] = (float)(v - (double)hi);
+}
+
+// grid = (B super-blocks, S slices), 256 lanes.  acc = [S + K slots][{hi, lo}][D][pad], qsum = [S + K slots][pad].
+template <int D, int QS>
+__global__ __launch_bounds__(256, 2) void accel_sym3l_kernel(KArgs a) {
+    constexpr int PAIRS = 4;
+    constexpr unsigned kSumBytes = (unsigned)PAIRS * D * 256u * sizeof(double2);          // home level 3: [PAIRS*D][256] double2
+    constexpr unsigned kVisBytes = 4u * kSymChunkGroups * kSymGroup * sizeof(float4);     // visitor level 2: [wave][group][visitor] {x, y, z, Q}
+    __shared__ __attribute__((aligned(16))) char smem[kSumBytes + kVisBytes];
+    double2* __restrict__ sums = reinterpret_cast<double2*>(smem);
+    float4* __restrict__ vbuf = reinterpret_cast<float4*>(smem + kSumBytes);
+
+    SymPlan P;
+    if (!sym_make_plan(a.pad, &P) || P.B != gridDim.x || P.S != gridDim.y) return;   // the launcher checked; a guard, not a path
+    const unsigned A = blockIdx.x, s = blockIdx.y;
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    // measurement only, as in accel_fast3l_kernel (a.clk is null in every other launch): the shader clock this workgroup held
+    unsigned long long clk_r0 = 0, clk_t0 = 0;
+    if (a.clk) {
+        clk_r0 = __builtin_amdgcn_s_memrealtime();
+        clk_t0 = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+    }
+    const size_t pad = a.pad;
+    const float* __restrict__ tp = a.pos_all + (size_t)a.tgt_chunk * D * pad;
+    const float* __restrict__ mp = a.mass_all + (size_t)a.tgt_chunk * pad;
+    const f2 bias = f2{kTiny, kTiny};
+    const size_t slot_stride = 2 * (size_t)D * pad;   // floats between the hi planes of consecutive slots
+
+    // after t moves a lane holds the visitor that started (t * delta) lanes further on (mod 64); delta is read off the move itself
+    const unsigned delta = ((unsigned)__builtin_amdgcn_update_dpp((int)lane, (int)lane, 0x13C, 0xF, 0xF, false) - lane) & 63u;
+
+    if (sym_clears_last_slot(P, A)) {   // rows nobody else writes (sym_plan.h)
+        float* __restrict__ hi = a.acc + (size_t)(P.S + P.K - 1u) * slot_stride;
+        const unsigned len = kSymSuper / P.S;
+        for (unsigned t = tid; t < len; t += 256u) {
+            const size_t v = (size_t)A * kSymSuper + (size_t)s * len + t;
+            if (v < pad) {
+#pragma unroll
+                for (int k = 0; k < 2 * D; ++k) hi[(size_t)k * pad + v] = 0.0f;
+                if (QS) a.qsum[(size_t)(P.S + P.K - 1u) * pad + v] = 0.0f;
+            }
+        }
+    }
+
+    for (unsigned hp = 0; hp < kSymSuper / kSymHomePass; ++hp) {
+        const unsigned h0 = A * kSymSuper + hp * kSymHomePass;
+        if (h0 >= a.pad) break;   // ragged last super-block
+        const unsigned tgt0 = h0 + tid;
+        f2 ix[PAIRS], iy[PAIRS], iz[PAIRS], hm[PAIRS], qq[QS ? PAIRS : 1];
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) {
+            const unsigned i0 = tgt0 + (2 * q) * 256u, i1 = i0 + 256u;
+            ix[q] = f2{tp[i0], tp[i1]};
+            iy[q] = f2{tp[pad + i0], tp[pad + i1]};
+            iz[q] = (D == 3) ? f2{tp[2 * pad + i0], tp[2 * pad + i1]} : f2{0.f, 0.f};
+            hm[q] = f2{mp[i0], mp[i1]};
+            if (QS) qq[q] = f2{0.f, 0.f};
+        }
+#pragma unroll
+        for (int c = 0; c < PAIRS * D; ++c) sums[c * 256 + tid] = double2{0.0, 0.0};   // own slots only: no barrier needed
+
+        SymWalk nw;
+        nw.k = 0u; nw.c = ~0u;
+        bool more = sym_next_chunk(P, A, s, &nw);
+        f2 nxy = f2{0.f, 0.f}, nzm = f2{0.f, 0.f};
+        if (more) load_visitor<D>(tp, mp, a.pad, nw.first + lane, nxy, nzm);
+        while (more) {
+            const SymWalk cw = nw;
+            f2 ox[PAIRS], oy[PAIRS], oz[PAIRS];
+#pragma unroll
+            for (int q = 0; q < PAIRS; ++q) ox[q] = oy[q] = oz[q] = f2{0.f, 0.f};
+#pragma unroll 1
+            for (unsigned g = 0; g < cw.groups; ++g) {
+                f2 vxy = nxy, vzm = nzm;
+                // the next group's bodies fly while this one rotates
+                if (g + 1u < cw.groups) {
+                    load_visitor<D>(tp, mp, a.pad, cw.first + (g + 1u) * kSymGroup + lane, nxy, nzm);
+                } else {
+                    more = sym_next_chunk(P, A, s, &nw);
+                    if (more) load_visitor<D>(tp, mp, a.pad, nw.first + lane, nxy, nzm);
+                }
+                float4* __restrict__ vslot = vbuf + (wave * kSymChunkGroups + g) * kSymGroup;
+                // cleared here rather than by a branch on the first block: the block loop's body stays one basic block (a branch
+                // made the compiler sink the home sums' arithmetic of all eight steps below it, at 256 VGPRs and spills)
+                vslot[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+                f2 ax[PAIRS], ay[PAIRS], az[PAIRS];
+#pragma unroll
+                for (int q = 0; q < PAIRS; ++q) ax[q] = ay[q] = az[q] = f2{0.f, 0.f};
+#pragma unroll 1
+                for (unsigned blk = 0; blk < 8u; ++blk) {
+                    f2 vax = f2{0.f, 0.f}, vay = f2{0.f, 0.f}, vaz = f2{0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        sym_step<D, PAIRS>(vxy, vzm, ix, iy, iz, hm, ax, ay, az, vax, vay, vaz, bias);
+                        ror1(vxy); ror1(vzm); ror1(vax); ror1(vay);
+                        if (D == 3) ror1(vaz);
+                        __builtin_amdgcn_sched_barrier(0);   // one step at a time: interleaving the unrolled steps only costs registers
+                    }
+                    // visitor level 1 -> level 2, in the wave's slot of the visitor that now sits in this lane
+                    const unsigned vid = (lane + (blk + 1u) * 8u * delta) & 63u;
+                    const float bx = vax.x + vax.y, by = vay.x + vay.y, bz = (D == 3) ? vaz.x + vaz.y : 0.0f;
+                    float4 cur = vslot[vid];
+                    cur.x += bx; cur.y += by; cur.z += bz;
+                    if (QS) cur.w = __builtin_fmaf(bz, bz, __builtin_fmaf(by, by, __builtin_fmaf(bx, bx, cur.w)));
+                    vslot[vid] = cur;
+                }
+                // home level 1 -> level 2
+#pragma unroll
+                for (int q = 0; q < PAIRS; ++q) { ox[q] += ax[q]; oy[q] += ay[q]; if (D == 3) oz[q] += az[q]; }
+                if (QS) {
+#pragma unroll
+                    for (int q = 0; q < PAIRS; ++q) {
+                        qq[q] = __builtin_elementwise_fma(ax[q], ax[q], qq[q]);
+                        qq[q] = __builtin_elementwise_fma(ay[q], ay[q], qq[q]);
+                        if (D == 3) qq[q] = __builtin_elementwise_fma(az[q], az[q], qq[q]);
+                    }
+                }
+            }
+            // home level 2 -> level 3: the lane's own fp64 slots
+#pragma unroll
+            for (int q = 0; q < PAIRS; ++q) {
+                double2 v = sums[(q * D + 0) * 256 + tid];
+                v.x += (double)ox[q].x; v.y += (double)ox[q].y;
+                sums[(q * D + 0) * 256 + tid] = v;
+                v = sums[(q * D + 1) * 256 + tid];
+                v.x += (double)oy[q].x; v.y += (double)oy[q].y;
+                sums[(q * D + 1) * 256 + tid] = v;
+                if (D == 3) {
+                    v = sums[(q * D + 2) * 256 + tid];
+                    v.x += (double)oz[q].x; v.y += (double)oz[q].y;
+                    sums[(q * D + 2) * 256 + tid] = v;
+                }
+            }
+            if (!cw.two_sided) continue;   // own block: the visitors' sums are dropped (workgroup-uniform)
+            // visitor level 2 -> level 3: the four waves' sums of one visitor in wave order, onto what the earlier home passes left
+            __syncthreads();
+            if (tid < cw.groups * kSymGroup) {
+                const unsigned g = tid >> 6;
+                const size_t v = (size_t)cw.first + tid;
+                const float4 b0 = vbuf[(0u * kSymChunkGroups + g) * kSymGroup + lane], b1 = vbuf[(1u * kSymChunkGroups + g) * kSymGroup + lane];
+                const float4 b2 = vbuf[(2u * kSymChunkGroups + g) * kSymGroup + lane], b3 = vbuf[(3u * kSymChunkGroups + g) * kSymGroup + lane];
+                float* __restrict__ hi = a.acc + (size_t)(P.S + cw.k - 1u) * slot_stride;
+                float* __restrict__ lo = hi + (size_t)D * pad;
+                double rx = -((((double)b0.x + (double)b1.x) + (double)b2.x) + (double)b3.x);
+                double ry = -((((double)b0.y + (double)b1.y) + (double)b2.y) + (double)b3.y);
+                double rz = -((((double)b0.z + (double)b1.z) + (double)b2.z) + (double)b3.z);
+                if (hp != 0u) {
+                    rx += (double)hi[v] + (double)lo[v];
+                    ry += (double)hi[pad + v] + (double)lo[pad + v];
+                    if (D == 3) rz += (double)hi[2 * pad + v] + (double)lo[2 * pad + v];
+                }
+                store_hi_lo(hi, lo, v, rx);
+                store_hi_lo(hi, lo, pad + v, ry);
+                if (D == 3) store_hi_lo(hi, lo, 2 * pad + v, rz);
+                if (QS) {
+                    float* __restrict__ qo = a.qsum + (size_t)(P.S + cw.k - 1u) * pad + v;
+                    const float qv = ((b0.w + b1.w) + b2.w) + b3.w;
+                    *qo = (hp != 0u) ? *qo + qv : qv;
+                }
+            }
+            __syncthreads();   // everybody has read the visitors' slots before the next chunk overwrites them
+        }
+
+        // the home pass's sums: slot s, rows of A
+        float* __restrict__ hi = a.acc + (size_t)s * slot_stride;
+        float* __restrict__ lo = hi + (size_t)D * pad;
+        float* __restrict__ qout = QS ? a.qsum + (size_t)s * pad : nullptr;
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q) {
+            const double2 vx = sums[(q * D + 0) * 256 + tid], vy = sums[(q * D + 1) * 256 + tid];
+            const double2 vz = (D == 3) ? sums[(q * D + (D == 3 ? 2 : 0)) * 256 + tid] : double2{0.0, 0.0};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const unsigned i = tgt0 + (2 * q + h) * 256u;
+                if (!a.bad_flag[i]) {   // flagged targets belong to the guarded side path + scatter_close_kernel
+                    store_hi_lo(hi, lo, i, h ? vx.y : vx.x);
+                    store_hi_lo(hi, lo, pad + i, h ? vy.y : vy.x);
+                    if (D == 3) store_hi_lo(hi, lo, 2 * pad + i, h ? vz.y : vz.x);
+                    if (QS) qout[i] = h ? qq[q].y : qq[q].x;
+                } else if (QS) {
+                    qout[i] = __builtin_inff();   // a close-set target keeps no spread sum: it is always a suspect
+                }
+            }
+        }
+    }
+    if (a.clk) {
+        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+        if (tid == 0) {
+            const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+            a.clk[2 * wg] = t1 - clk_t0;
+            a.clk[2 * wg + 1] = r1 - clk_r0;
+        }
+    }
+}
+
+}  // namespace
+
+// the table entry of this unit (force_launch.hip appends it to force_kernel.hip's)
+KernelVariant sym_kernel_variant() {
+    KernelVariant v = {};
+    v.name = "sympk3l_t8_w3";
+    v.tpl = 8;
+    v.k2 = accel_sym3l_kernel<2, 0>; v.k3 = accel_sym3l_kernel<3, 0>;
+    v.qs2 = accel_sym3l_kernel<2, 1>; v.qs3 = accel_sym3l_kernel<3, 1>;
+    v.fast = 1;
+    v.planes = 2;
+    v.sym = 1;
+    v.stamps = 1;
+    return v;
+}
+
+}  // namespace nbx

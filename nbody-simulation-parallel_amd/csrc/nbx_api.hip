@@ -178,6 +178,9 @@ namespace {
 
 constexpr int kEventPairs = 512;
 constexpr int kMaxSplits = 256;
+#ifndef NBX_SYM_DEFAULT
+#define NBX_SYM_DEFAULT 0
+#endif
 constexpr int kPhiSlices = 16;
 constexpr int kGraphMinSteps = 4;   // nbx_ctx_step replays a captured step from this many steps on
 // Mixed mode: selection rule |a|^2 < (sigma u / tol)^2 Q (force_kernel.hip).  The sigma factor is a calibration of the DEFAULT
@@ -262,6 +265,22 @@ int ensure_stage(nbx_ctx* c, size_t bytes) {
     return NBX_OK;
 }
 
+// The symmetric own-shard pass (force_sym_kernel.hip) applies where a pass's sources are exactly the context's own bodies: a
+// single-shard context of at least two super-blocks whose S + K slots of planes fit (sym_plan.h; 2.25 GiB at N = 2^20, D = 3).
+bool sym_applies(const nbx_ctx* c, int sym) {
+    const int slots = variant_sym_slots(sym, c->pad);
+    return c->n_shards == 1 && slots > 0 &&
+           (size_t)slots * variant_planes(sym) * c->dim * c->pad * sizeof(float) <= ((size_t)48 << 30);
+}
+// ... everywhere else a context that was asked for it silently keeps the one-sided three-level kernel
+int one_sided_of_sym() {
+    const int v = variant_by_name("fastpk3l_t8_w3_u4");
+    return v >= 0 ? v : default_fast_two_rcp_variant();
+}
+// 1: a context that was given neither a variant nor a slice count runs the symmetric pass where it applies.  The library's default variant keeps its
+// name (the one-sided three-level kernel, which every multi-shard pass and every small shard runs).
+constexpr int kSymWhereItApplies = NBX_SYM_DEFAULT;
+
 // The variant actually launched: the caller's choice (or the default), demoted to the exact default when
 // the fast path's preconditions do not hold for this context.
 int effective_variant(const nbx_ctx* c) {
@@ -275,6 +294,14 @@ int effective_variant(const nbx_ctx* c) {
     if (variant_is_fast(v) && c->force_exact) v = default_exact_variant();
     else if (variant_needs_extent(v) && !c->extent_ok) v = default_fast_two_rcp_variant();
     if (c->refine_tol > 0.0 && variant_is_fast(v) && !variant_has_qsum(v)) v = default_fast_two_rcp_variant();
+    if (variant_is_sym(v)) {
+        if (!sym_applies(c, v)) v = one_sided_of_sym();
+    } else if (kSymWhereItApplies && c->variant_req < 0 && !c->splits_user && v == default_variant() && v == one_sided_of_sym()) {
+        const int sym = variant_by_name("sympk3l_t8_w3");
+        // ... and pays: its workgroups hold 8,192 home bodies each, so a small shard leaves most of the chip idle (two
+        // workgroups per CU are resident; below one full round of them the one-sided kernel's finer grid wins)
+        if (sym >= 0 && sym_applies(c, sym) && variant_sym_workgroups(sym, c->pad) >= 2 * c->num_cus) v = sym;
+    }
     return v;
 }
 
@@ -312,6 +339,7 @@ int auto_splits(const nbx_ctx* c, int variant) {
 // Source slices of the next launch of `variant`: the caller's count or the automatic one, raised to what the kernel's
 // fp32 second-level sums need, and such that slices x planes per slice stays within kMaxSplits planes.
 int slices_for(const nbx_ctx* c, int variant) {
+    if (variant_is_sym(variant)) return variant_sym_slots(variant, c->pad);   // the plan's own count: S slices + K reaction slots
     int s = c->splits_user ? c->user_slices : auto_splits(c, variant);
     if (const int cap = variant_max_tiles_per_slice(variant)) {  // a caller's slice count is a lower bound
         const unsigned tiles = (unsigned)c->n_shards * (c->pad / kTile);
@@ -667,7 +695,8 @@ int nbx_ctx_create(nbx_ctx** out, int device, int dim, size_t n_total, int n_sha
         // the close-set side path has its own), the close-set lists, and -- for an unsharded context, whose exchange
         // buffers are always its own -- the fp32 source arrays.  Anything else falls through to its own allocation.
         const size_t body = (size_t)(2 * dim + 1) * sizeof(double);
-        const int splits = auto_splits(c, c->variant);
+        const int launched = effective_variant(c);   // the symmetric pass where it applies: its S + K slots (same planes per slot)
+        const int splits = variant_is_sym(launched) ? variant_sym_slots(launched, c->pad) : auto_splits(c, c->variant);
         size_t want = 2 * arena_round((size_t)dim * pad * sizeof(double)) + arena_round(pad * sizeof(double));
         want += arena_round(n_total * body + 16) + arena_round(3 * sizeof(unsigned long long));
         want += 2 * arena_round((size_t)splits * variant_planes(c->variant) * dim * pad * sizeof(float));   // acc and the close-set side path's
@@ -888,7 +917,11 @@ int nbx_ctx_get_aux(nbx_ctx* c, double* out) {
 int nbx_ctx_effective_tuning(nbx_ctx* c, int* variant, int* source_splits) {
     if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
     const int v = effective_variant(c);
-    if (variant) *variant = v;
+    // a context asked for the symmetric pass where it does not apply reports what it was asked for: the one-sided kernel it
+    // runs instead evaluates the same pairs in the same arithmetic
+    const bool sym_kept = c->variant_req >= 0 && variant_is_sym(c->variant_req) && !variant_is_sym(v) && v == one_sided_of_sym() &&
+                          !(c->softening > 0.0) && !c->force_exact;
+    if (variant) *variant = sym_kept ? c->variant_req : v;
     if (source_splits) *source_splits = slices_for(c, v);
     return NBX_OK;
 }

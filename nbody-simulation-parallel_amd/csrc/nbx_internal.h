@@ -165,11 +165,15 @@ struct KernelVariant {
     int planes;              // fp32 planes of acc written per source slice: 1, or 2 = {hi, lo} of an fp64 sum (strict kernel)
     int aux;                 // 1: the kernel itself writes KArgs::qsum (the strict kernel's magnitude-sum build)
     int stamps;              // 1: the kernel writes KArgs::clk when it is non-null (measurement)
+    int sym;                 // 1: the symmetric own-shard pass (force_sym_kernel.hip): own launch shape, S + K slots of `planes` planes (sym_plan.h)
 };
 // force_kernel.hip
 const KernelVariant* kernel_variants(int* count);
+// force_sym_kernel.hip
+KernelVariant sym_kernel_variant();
 struct CloseKernels { void (*classify[2])(KArgs); void (*classify_src[2])(KArgs); void (*refine[2])(KArgs); void (*scatter[2])(KArgs); void (*potential[2])(KArgs); void (*potential_soft[2])(KArgs); void (*potential_newton[2])(KArgs);
-                      void (*refine_select[2])(KArgs); void (*strict_list[2])(KArgs); void (*refine_fold[2])(KArgs); };  // [0]: D=2, [1]: D=3
+                      void (*refine_select[2])(KArgs); void (*strict_list[2])(KArgs); void (*refine_fold[2])(KArgs);
+                      void (*close_only[2])(KArgs); };  // [0]: D=2, [1]: D=3
 CloseKernels close_kernels();
 
 // close_hash.hip
@@ -206,6 +210,9 @@ int variant_has_law_builds(int variant);  // softened / Newtonian builds of the 
 int variant_planes(int variant);          // fp32 planes of acc per source slice (2: strict fp64 kernel)
 int variant_has_qsum(int variant);        // the variant has a build that writes qsum (mixed mode possible)
 int variant_writes_aux(int variant);      // the variant's own kernel writes qsum (strict magnitude-sum build)
+int variant_is_sym(int variant);           // the symmetric own-shard pass: launched for single-shard contexts only (sym_plan.h)
+int variant_sym_slots(int variant, unsigned pad);   // its S + K slots for a shard of `pad` bodies; 0: no symmetric decomposition
+int variant_sym_workgroups(int variant, unsigned pad);   // workgroups of its launch (B x S); 0: no symmetric decomposition
 int variant_has_clock_stamps(int variant);   // the variant's kernel honours AccelLaunch::clk (the three-level kernel)
 // demangled symbol of the kernel launch_accel launches for (variant, dim, law, softened, mixed mode) -- the name rocprofv3 prints
 int variant_kernel_symbol(int variant, int dim, int law, int soft, int qsum, char* buf, size_t len);
