@@ -19,7 +19,7 @@ all: lib oracle nbody_sim
 lib: $(LIB)
 
 OBJS := $(CSRC)/force_kernel.o $(CSRC)/force_sym_kernel.o $(CSRC)/force_launch.o \
-        $(CSRC)/state_kernels.o $(CSRC)/nbx_api.o $(CSRC)/nbx_node.o $(CSRC)/leaf_pair_kernel.o $(CSRC)/leaf_far_kernel.o $(CSRC)/close_hash.o $(CSRC)/measure_kernels.o
+        $(CSRC)/state_kernels.o $(CSRC)/nbx_api.o $(CSRC)/nbx_node.o $(CSRC)/leaf_pair_kernel.o $(CSRC)/leaf_far_kernel.o $(CSRC)/octree_device.o $(CSRC)/close_hash.o $(CSRC)/measure_kernels.o
 # name of the force-kernel variant used when the caller does not pick one
 # (round 4: the three-level summation build -- same pair arithmetic, fp32 errors ~3x smaller for +1.5 % time)
 DEFAULT_VARIANT ?= fastpk3l_t8_w3_u4
@@ -56,12 +56,16 @@ $(CSRC)/measure_kernels.o: $(CSRC)/measure_kernels.hip $(CSRC)/nbx_internal.h $(
 $(CSRC)/close_hash.o: $(CSRC)/close_hash.hip $(CSRC)/nbx_internal.h $(CSRC)/device_sort.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/leaf_pair_kernel.o: $(CSRC)/leaf_pair_kernel.hip $(CSRC)/leaf_plan.h $(CSRC)/leaf_plan_device.h $(CSRC)/leaf_law.h $(CSRC)/leaf_far.h $(CSRC)/device_sort.h $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
+$(CSRC)/leaf_pair_kernel.o: $(CSRC)/leaf_pair_kernel.hip $(CSRC)/leaf_plan.h $(CSRC)/leaf_plan_device.h $(CSRC)/leaf_law.h $(CSRC)/leaf_far.h $(CSRC)/octree_device.h $(CSRC)/device_sort.h $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) $(LEAF_DEFS) -c $< -o $@
 
 # the far field of a leaf plan: moment and far kernels
 $(CSRC)/leaf_far_kernel.o: $(CSRC)/leaf_far_kernel.hip $(CSRC)/leaf_far.h $(CSRC)/leaf_law.h $(CSRC)/nbx_internal.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the octree built on the device.  -ffp-contract=off: a body's cell index must round like the host builder's two-step arithmetic
+$(CSRC)/octree_device.o: $(CSRC)/octree_device.hip $(CSRC)/octree_device.h $(CSRC)/leaf_far.h $(CSRC)/device_sort.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 
 $(LIB): $(OBJS) $(CSRC)/libnbody_hip.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJS) -ldl -Wl,--version-script=$(CSRC)/libnbody_hip.map

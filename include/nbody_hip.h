@@ -224,6 +224,36 @@ int nbx_leaf_plan_get_cells(nbx_leaf_plan* plan, double* mass_out, double* com_o
  * 0 otherwise); kernel_ms of the evaluation itself keeps meaning the near-field pair kernel.  Any pointer may be NULL. */
 int nbx_leaf_plan_cell_info(nbx_leaf_plan* plan, size_t* n_cells, size_t* far_entries, float* moments_ms, float* far_ms);
 
+/* ---- the octree built on the device ---------------------------------------------------------------
+ * A fixed-depth octree (quadtree in 2D) over the bodies RESIDENT in a single-shard context, with the near and far lists of a
+ * Barnes-Hut walk with opening angle theta (octree.cpp:129-151's test on grid boxes): the tree, both lists, the plan's layout and
+ * its far field are all made on the device, on the context's stream; 64 bytes of counts and the planner's 64-byte summary are
+ * all the host reads.  The reference rebuilds its tree in every force call (methods.cpp:377-401); nbx_leaf_plan_rebuild_octree
+ * is that rebuild, and nbx_leaf_plan_step_octree a whole Barnes-Hut step loop without the bodies or the tree leaving the GPU.
+ * The structure is, word for word, the eight arrays the host builders make (leaves.octree_cells, build_octree_cells<D>):
+ * leaves = non-empty cells of the 2^depth grid over the 1 %-padded bounding box, in Morton order; cells = the non-empty nodes
+ * of levels 1 .. depth; per leaf a near list (itself first) and a far list (coarse levels first).  0 <= depth <= 10; theta >= 0
+ * and finite (theta = 0 accepts nothing: every leaf is on every near list).  The plan is bound to the context's device,
+ * dimension and body count and works with every nbx_leaf_plan_* call.
+ * NBX_ERR_INVALID: null pointers, a context of several shards or without bodies, depth or theta out of range, a coordinate
+ * that is not finite (no plan is made), more than 0xfffffff0 near or far entries.  NBX_ERR_STATE: nothing uploaded yet. */
+int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* ctx, int depth, double theta);
+/* Builds the structure again, with the same depth and theta, from the context's current positions.  The plan's device blocks
+ * are reused where they fit.  NBX_ERR_STATE for a plan not made by nbx_leaf_plan_create_octree.  After a refused rebuild the
+ * plan holds no structure (evaluations return NBX_ERR_STATE) until a rebuild succeeds. */
+int nbx_leaf_plan_rebuild_octree(nbx_leaf_plan* plan, nbx_ctx* ctx);
+/* Lengths of the structure built on the device: leaf_offsets, list_offsets and far_offsets have n_leaves + 1 words, leaf_bodies
+ * one per body, list_sources near_entries, the two cell arrays n_cells each, far_cells far_entries.  Any pointer may be NULL.
+ * NBX_ERR_STATE on plans not built on the device. */
+int nbx_leaf_plan_structure_sizes(const nbx_leaf_plan* plan, size_t* n_leaves, size_t* near_entries, size_t* n_cells, size_t* far_entries);
+/* Copies the structure to the host (any pointer may be NULL) and synchronises.  NBX_ERR_STATE on plans not built on the device. */
+int nbx_leaf_plan_get_structure(nbx_leaf_plan* plan, uint32_t* leaf_offsets, uint32_t* leaf_bodies, uint32_t* list_offsets, uint32_t* list_sources,
+                                uint32_t* cell_first_leaf, uint32_t* cell_leaf_count, uint32_t* far_offsets, uint32_t* far_cells);
+/* nsteps x { rebuild when rebuild_every > 0 and step % rebuild_every == 0 (steps count from 0); forces_ctx(NULL, NULL);
+ * kick_drift }.  rebuild_every = 0 never rebuilds and equals nbx_leaf_plan_step.  Afterwards the plan holds the last step's
+ * sums and the last structure built. */
+int nbx_leaf_plan_step_octree(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, double dt, int nsteps, int rebuild_every);
+
 /* ---- device-resident context ------------------------------------------------------------------
  * A context owns the targets of ONE shard of an N-body system on ONE device and a full-length
  * fp32 copy of all N sources.  n_shards = 1, shard = 0 is the single-GPU case.  With n_shards = G

@@ -53,6 +53,11 @@ ABI = [
     ("nbx_leaf_plan_set_cells", _i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("nbx_leaf_plan_get_cells", _i, [_vp, _vp, _vp]),
     ("nbx_leaf_plan_cell_info", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _pf, _pf]),
+    ("nbx_leaf_plan_create_octree", _i, [_c.POINTER(_vp), _vp, _i, _d]),
+    ("nbx_leaf_plan_rebuild_octree", _i, [_vp, _vp]),
+    ("nbx_leaf_plan_structure_sizes", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz)]),
+    ("nbx_leaf_plan_get_structure", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("nbx_leaf_plan_step_octree", _i, [_vp, _vp, _i, _d, _d, _i, _i]),
     ("nbx_ctx_create", _i, [_c.POINTER(_vp), _i, _i, _sz, _i, _i]),
     ("nbx_ctx_destroy", _i, [_vp]),
     ("nbx_ctx_set_stream", _i, [_vp, _vp]),
@@ -292,6 +297,42 @@ class LeafPlan:
         _check(self.lib, self.lib.nbx_leaf_plan_create(ctypes.byref(h), device, dim, self.n, arrs[0].ctypes.data, arrs[1].ctypes.data,
                                                        arrs[0].size - 1, arrs[2].ctypes.data, arrs[3].ctypes.data), "nbx_leaf_plan_create")
         self.h = h
+
+    @classmethod
+    def from_octree(cls, ctx: "Context", depth: int, theta: float) -> "LeafPlan":
+        """A fixed-depth octree with near and far lists built ON THE DEVICE from the bodies resident in `ctx`
+        (nbx_leaf_plan_create_octree): the structure leaves.octree_cells(bodies, dim, depth, theta) makes on the host, without
+        the bodies or the tree crossing PCIe."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.n, self.dim, self.device = int(ctx.n_total), int(ctx.dim), ctx.device
+        h = ctypes.c_void_p()
+        _check(self.lib, self.lib.nbx_leaf_plan_create_octree(ctypes.byref(h), ctx.h, int(depth), float(theta)), "nbx_leaf_plan_create_octree")
+        self.h = h
+        return self
+
+    def rebuild(self, ctx: "Context"):
+        """The octree again, same depth and theta, from the context's current positions (nbx_leaf_plan_rebuild_octree)."""
+        self._ck(self.lib.nbx_leaf_plan_rebuild_octree(self.h, ctx.h), "nbx_leaf_plan_rebuild_octree")
+
+    def structure_sizes(self):
+        """(n_leaves, near_entries, n_cells, far_entries) of the structure built on the device."""
+        v = [ctypes.c_size_t() for _ in range(4)]
+        self._ck(self.lib.nbx_leaf_plan_structure_sizes(self.h, *[ctypes.byref(x) for x in v]), "nbx_leaf_plan_structure_sizes")
+        return tuple(x.value for x in v)
+
+    def structure(self):
+        """The eight arrays of leaves.octree_cells, read back from the device: (leaf_offsets, leaf_bodies, list_offsets,
+        list_sources, cell_first_leaf, cell_leaf_count, far_offsets, far_cells), all uint32 (nbx_leaf_plan_get_structure)."""
+        nl, near, nc, far = self.structure_sizes()
+        out = [np.zeros(k, dtype=np.uint32) for k in (nl + 1, self.n, nl + 1, near, nc, nc, nl + 1, far)]
+        self._ck(self.lib.nbx_leaf_plan_get_structure(self.h, *[a.ctypes.data if a.size else None for a in out]), "nbx_leaf_plan_get_structure")
+        return tuple(out)
+
+    def step_octree(self, ctx: "Context", law: int, G: float, dt: float, nsteps: int, rebuild_every: int = 1):
+        """nsteps x {rebuild every `rebuild_every` steps; forces_ctx(fetch=False); kick_drift} (nbx_leaf_plan_step_octree)."""
+        self._ck(self.lib.nbx_leaf_plan_step_octree(self.h, ctx.h, int(law), float(G), float(dt), int(nsteps), int(rebuild_every)),
+                 "nbx_leaf_plan_step_octree")
 
     def close(self):
         if getattr(self, "h", None):

@@ -40,6 +40,7 @@
 #include "leaf_law.h"
 #include "leaf_far.h"
 #include "leaf_plan_device.h"
+#include "octree_device.h"
 
 #include <cmath>
 #include <cstdio>
@@ -890,6 +891,17 @@ struct nbx_leaf_plan {
     // set_cells, destroy) clears it; nbx_leaf_plan_get_cells and the far pass of nbx_leaf_plan_time_kernel rely on that.
     bool cells_evaluated = false;
     bool cells_timed = false;       // ... and it recorded the four events
+    // ---- a structure built on the device (nbx_leaf_plan_create_octree; octree_device.h) ----
+    bool octree = false;            // made by nbx_leaf_plan_create_octree
+    bool octree_built = false;      // ... and its last build went through (a refused rebuild leaves nothing to evaluate)
+    int octree_depth = 0;
+    double octree_theta = 0.0;
+    char* tree_arena = nullptr;     // the builder's block: the tree, six of the eight structure arrays, scratch
+    size_t tree_arena_bytes = 0;
+    nbx_octree::TreeLayout tree_layout{};
+    nbx_octree::Tree tree;
+    nbx_octree::Counts counts_host{};     // the builder's 64 bytes land here
+    const uint32_t* list_sources_dev = nullptr;   // in the arena
 };
 
 namespace {
@@ -1337,9 +1349,182 @@ void plan_release_cells(nbx_leaf_plan* p, bool device_idle, bool events) {
         }
     }
 }
+
+// A block of at least `bytes`: the one the plan holds when it is large enough, else that one parked (the caller has made sure that
+// nothing on the device uses it) and another taken.
+int plan_fit_arena(nbx_leaf_plan* p, size_t bytes, char** arena, size_t* arena_bytes) {
+    if (*arena && *arena_bytes >= bytes) return NBX_OK;
+    if (*arena) park_arena(p->device, *arena, *arena_bytes);
+    *arena = nullptr;
+    *arena_bytes = 0;
+    NBX_HIP_TRY(take_arena(p->device, bytes, arena, arena_bytes));
+    return NBX_OK;
+}
+
+// Build (or build again) the octree of a plan made by nbx_leaf_plan_create_octree from the context's current positions, and lay the
+// plan and its far field out, all on the context's stream.  Two read-backs of 64 bytes: the builder's counts, the planner's summary.
+// A refusal leaves the plan without a structure (octree_built = false) but with its blocks, for the next build.
+int plan_build_octree(nbx_leaf_plan* p, nbx_ctx* c) {
+    using namespace nbx_leaf_dev;
+    hipStream_t s = c->stream;
+    if (int rc = plan_order_after_last(p, s)) return rc;
+    p->octree_built = false;
+    p->evaluated = false;
+    p->cells_evaluated = p->cells_timed = false;
+    p->far = nbx_far::FarDevice();
+    p->far_entries = 0;
+    const int dim = p->dim, depth = p->octree_depth;
+    const nbx_octree::TreeLayout& T = p->tree_layout;
+    if (int rc = plan_fit_arena(p, T.total, &p->tree_arena, &p->tree_arena_bytes)) return rc;
+    NBX_HIP_TRY(nbx_octree::enqueue_build(c->x64, c->pad, p->n, dim, depth, p->octree_theta, p->tree_arena, T, s, &p->counts_host, &p->tree));
+    NBX_HIP_TRY(hipStreamSynchronize(s));   // the counts are here; whatever used the plan's blocks before is over
+    if (int rc = plan_mark_done(p, s)) return rc;
+    const nbx_octree::Counts C = p->counts_host;
+    if (C.bad) return fail(NBX_ERR_INVALID, "a coordinate is not finite");
+    if (C.near_entries > 0xfffffff0ull) return fail(NBX_ERR_INVALID, "near lists too long");
+    if (C.far_entries > 0xfffffff0ull) return fail(NBX_ERR_INVALID, "far lists too long");
+    // the plan's block, sized by the counts (leaf_plan_device.h)
+    const Bounds b{p->n, C.n_leaves, p->n, (size_t)C.near_entries};
+    const Layout L = make_layout(b, dim);
+    if (int rc = plan_fit_arena(p, L.total, &p->arena, &p->arena_bytes)) return rc;
+    const DevicePlan d = plan_pointers(p->arena, L);
+    p->xp = d.xp; p->sums = d.sums; p->pslot_body = d.pslot_body; p->body_slot = d.body_slot; p->ops = d.ops; p->blocks = d.blocks;
+    p->subs = d.subs; p->packs = d.packs; p->max_mass = d.max_mass;
+    p->unit_off = reinterpret_cast<uint32_t*>(p->arena + L.unit_off);
+    p->unit_host.clear();
+    p->n_leaves = C.n_leaves;
+    uint32_t* const list_sources = reinterpret_cast<uint32_t*>(p->arena + L.list_sources);
+    p->list_sources_dev = list_sources;
+    // the cells' block: far lists, the far pass's waves, the moments, the far layout's scratch
+    const size_t nc = C.n_cells, nl = C.n_leaves;
+    const size_t sizes[7] = {(size_t)C.far_entries * 4, (size_t)C.far_blocks * sizeof(nbx_far::FarBlock), nl * 4 * sizeof(double), nc * sizeof(double),
+                             nc * (size_t)dim * sizeof(double), nc * sizeof(float4), nbx_octree::far_scratch_bytes(C.far_blocks)};
+    size_t offs[7], total = 0;
+    for (int i = 0; i < 7; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
+    if (int rc = plan_fit_arena(p, total, &p->cell_arena, &p->cell_arena_bytes)) return rc;
+    for (hipEvent_t* ev : {&p->evm0, &p->evm1, &p->evf0, &p->evf1})
+        if (!*ev) NBX_HIP_TRY(hipEventCreate(ev));
+    char* const cells = p->cell_arena;
+    uint32_t* const far_cells = reinterpret_cast<uint32_t*>(cells + offs[0]);
+    nbx_far::FarBlock* const far_blocks = reinterpret_cast<nbx_far::FarBlock*>(cells + offs[1]);
+    NBX_HIP_TRY(nbx_octree::enqueue_fill(p->n, dim, depth, p->octree_theta, p->tree_arena, T, list_sources, far_cells, s));
+    NBX_HIP_TRY(enqueue_device_plan(b, dim, p->tree.leaf_offsets, p->tree.leaf_bodies, p->tree.list_offsets, list_sources, NBX_LEAF_PACK != 0, p->arena, L, s,
+                                    &p->summary_host, true));
+    if (nc) NBX_HIP_TRY(nbx_octree::enqueue_far_layout(p->unit_off, C, p->tree_arena, T, far_blocks, cells + offs[6], s));
+    NBX_HIP_TRY(hipStreamSynchronize(s));
+    const Summary& S = p->summary_host;
+    if (S.err != kErrNone) return fail(NBX_ERR_INVALID, error_text(S.err));
+    p->device_planned = true;
+    p->waves = (int)S.waves; p->pslots = S.pslots; p->n_ops = S.n_ops; p->n_blocks = S.n_blocks; p->n_subs = S.n_subs; p->n_packs = S.n_packs;
+    if (nc) {
+        nbx_far::FarDevice& f = p->far;
+        f.xp = p->xp; f.unit_off = p->unit_off; f.sums = p->sums;
+        f.pslots = (uint32_t)p->pslots; f.n_leaves = C.n_leaves; f.n_cells = C.n_cells;
+        f.n_small = C.n_small; f.n_big = C.n_cells - C.n_small; f.n_blocks = C.far_blocks;
+        f.cell_first = p->tree.cell_first; f.cell_count = p->tree.cell_count;
+        f.small_cells = p->tree.small_cells; f.big_cells = p->tree.small_cells + C.n_small;
+        f.far_cells = far_cells; f.blocks = far_blocks;
+        f.leaf_mom = reinterpret_cast<double*>(cells + offs[2]);
+        f.cell_mass = reinterpret_cast<double*>(cells + offs[3]);
+        f.cell_com = reinterpret_cast<double*>(cells + offs[4]);
+        f.cell_rec = reinterpret_cast<float4*>(cells + offs[5]);
+        p->far_entries = (size_t)C.far_entries;
+    }
+    // as create_plan leaves a new plan: the sums of slots no workgroup writes are zero, the pads massless and far away
+    const size_t sum_bytes = (size_t)dim * p->pslots * sizeof(double);
+    NBX_HIP_TRY(hipMemsetAsync(p->sums, 0, sum_bytes ? sum_bytes : 8, s));
+    if (p->pslots) {
+        hipLaunchKernelGGL(leaf_init_pads_kernel, dim3((unsigned)((p->pslots + 255) / 256)), dim3(256), 0, s, p->pslot_body, (uint32_t)p->pslots, dim,
+                           reinterpret_cast<float*>(p->xp));
+        NBX_HIP_TRY(hipGetLastError());
+    }
+    p->octree_built = true;
+    return plan_mark_done(p, s);
+}
+
+int plan_needs_structure(const nbx_leaf_plan* p) {
+    if (p->octree && !p->octree_built) return fail(NBX_ERR_STATE, "the plan's last octree build was refused: rebuild it first");
+    return NBX_OK;
+}
+
+int plan_check_ctx(const nbx_leaf_plan* p, const nbx_ctx* c) {
+    if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
+        return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
+    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
+    return NBX_OK;
+}
 }  // namespace
 
 extern "C" {
+
+int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* c, int depth, double theta) {
+    if (!out) return fail(NBX_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    if (depth < 0 || depth > nbx_octree::kMaxDepth) return fail(NBX_ERR_INVALID, "depth must be in [0, 10]");
+    if (!(theta >= 0.0) || !std::isfinite(theta)) return fail(NBX_ERR_INVALID, "theta must be finite and >= 0");
+    if (c->n_shards != 1) return fail(NBX_ERR_INVALID, "the context must be a single-shard context");
+    if (c->n_total == 0 || c->n_total > ((size_t)1 << 31)) return fail(NBX_ERR_INVALID, "the context must hold between 1 and 2^31 bodies");
+    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
+    nbx_leaf_plan* p = new (std::nothrow) nbx_leaf_plan();
+    if (!p) return fail(NBX_ERR_ALLOC, "host allocation failed");
+    p->device = c->device; p->dim = c->dim; p->n = c->n_total;
+    p->octree = true; p->octree_depth = depth; p->octree_theta = theta;
+    p->tree_layout = nbx_octree::make_tree_layout(p->n, p->dim, depth);
+    DeviceScope scope;
+    hipError_t e = hipSetDevice(p->device);
+    if (e == hipSuccess) e = nbx::take_stream(p->device, &p->stream);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->done, hipEventDisableTiming);
+    int rc = e == hipSuccess ? plan_build_octree(p, c) : nbx::fail_hip(e, "creating the plan", __FILE__, __LINE__);
+    if (rc) { nbx_leaf_plan_destroy(p); return rc; }
+    *out = p;
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_rebuild_octree(nbx_leaf_plan* p, nbx_ctx* c) {
+    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
+    if (!p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
+    if (int rc = plan_check_ctx(p, c)) return rc;
+    DeviceScope scope;
+    if (int rc = plan_set_device(p)) return rc;
+    return plan_build_octree(p, c);
+}
+
+int nbx_leaf_plan_structure_sizes(const nbx_leaf_plan* p, size_t* n_leaves, size_t* near_entries, size_t* n_cells, size_t* far_entries) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (!p->octree || !p->octree_built) return fail(NBX_ERR_STATE, "the plan holds no structure built on the device");
+    if (n_leaves) *n_leaves = p->counts_host.n_leaves;
+    if (near_entries) *near_entries = (size_t)p->counts_host.near_entries;
+    if (n_cells) *n_cells = p->counts_host.n_cells;
+    if (far_entries) *far_entries = (size_t)p->counts_host.far_entries;
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_get_structure(nbx_leaf_plan* p, uint32_t* leaf_offsets, uint32_t* leaf_bodies, uint32_t* list_offsets, uint32_t* list_sources,
+                                uint32_t* cell_first_leaf, uint32_t* cell_leaf_count, uint32_t* far_offsets, uint32_t* far_cells) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (!p->octree || !p->octree_built) return fail(NBX_ERR_STATE, "the plan holds no structure built on the device");
+    DeviceScope scope;
+    int rc = plan_set_device(p);
+    if (rc) return rc;
+    hipStream_t s = p->stream;
+    if ((rc = plan_order_after_last(p, s))) return rc;
+    const nbx_octree::Counts& C = p->counts_host;
+    const size_t nl = C.n_leaves, nc = C.n_cells;
+    // the far lists live with the cells; nbx_leaf_plan_set_cells on this plan would have replaced them
+    const uint32_t* const far_dev = p->far.n_cells == nc ? p->far.far_cells : nullptr;
+    if (far_cells && C.far_entries && !far_dev) return fail(NBX_ERR_STATE, "the plan's cells were replaced by nbx_leaf_plan_set_cells");
+    struct Piece { uint32_t* to; const uint32_t* from; size_t words; };
+    const Piece pieces[8] = {{leaf_offsets, p->tree.leaf_offsets, nl + 1}, {leaf_bodies, p->tree.leaf_bodies, p->n}, {list_offsets, p->tree.list_offsets, nl + 1},
+                             {list_sources, p->list_sources_dev, (size_t)C.near_entries}, {cell_first_leaf, p->tree.cell_first, nc},
+                             {cell_leaf_count, p->tree.cell_count, nc}, {far_offsets, p->tree.far_offsets, nl + 1}, {far_cells, far_dev, (size_t)C.far_entries}};
+    for (const Piece& piece : pieces)
+        if (piece.to && piece.words) NBX_HIP_TRY(hipMemcpyAsync(piece.to, piece.from, piece.words * 4, hipMemcpyDeviceToHost, s));
+    NBX_HIP_TRY(hipStreamSynchronize(s));
+    return plan_mark_done(p, s);
+}
 
 int nbx_leaf_plan_create(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies,
                          size_t n_leaves, const uint32_t* list_offsets, const uint32_t* list_sources) {
@@ -1356,6 +1541,7 @@ int nbx_leaf_plan_destroy(nbx_leaf_plan* p) {
     bool idle = p->stream && hipStreamSynchronize(p->stream) == hipSuccess;
     plan_release_cells(p, idle && p->last_wait_ok, true);
     if (p->arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->arena, p->arena_bytes); else (void)hipFree(p->arena); }
+    if (p->tree_arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->tree_arena, p->tree_arena_bytes); else (void)hipFree(p->tree_arena); }
     if (p->forces && !p->forces_in_arena) (void)hipFree(p->forces);
     if (p->raw_arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->raw_arena, p->raw_arena_bytes); else (void)hipFree(p->raw_arena); }
     else if (p->raw) (void)hipFree(p->raw);
@@ -1385,6 +1571,7 @@ int nbx_leaf_plan_forces(nbx_leaf_plan* p, const void* bodies, size_t stride_byt
     const size_t min_stride = (size_t)(2 * p->dim + 1) * sizeof(double);
     if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
         return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
+    if (int src = plan_needs_structure(p)) return src;
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
@@ -1433,6 +1620,7 @@ int nbx_leaf_plan_forces_ctx(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, do
     if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
         return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
     if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
+    if (int src = plan_needs_structure(p)) return src;
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
@@ -1503,6 +1691,7 @@ int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double d
         return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
     if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
     if (nsteps == 0) return NBX_OK;
+    if (int src = plan_needs_structure(p)) return src;
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
@@ -1522,9 +1711,37 @@ int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double d
     return plan_mark_done(p, s);
 }
 
+int nbx_leaf_plan_step_octree(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
+    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "unknown law");
+    if (nsteps < 0 || rebuild_every < 0) return fail(NBX_ERR_INVALID, "nsteps and rebuild_every must be >= 0");
+    if (int rc = plan_check_ctx(p, c)) return rc;
+    if (rebuild_every > 0 && !p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
+    if (nsteps == 0) return NBX_OK;
+    DeviceScope scope;
+    int rc = plan_set_device(p);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = plan_order_after_last(p, s))) return rc;
+    const double signedG = (law == NBX_LAW_BRUTE) ? -G : G;
+    for (int k = 0; k < nsteps; ++k) {
+        if (rebuild_every > 0 && k % rebuild_every == 0 && (rc = plan_build_octree(p, c))) return rc;
+        if ((rc = plan_needs_structure(p))) return rc;
+        if ((rc = plan_enqueue_step(p, c, law, signedG, dt, s))) return rc;
+        p->evaluated = true; p->last_law = law;
+        p->last_signedG = signedG;
+        p->last_mass = c->m64; p->last_mass_stride = 1; p->last_ctx_id = c->id;
+        c->have_accel = false;                      // as nbx_leaf_plan_step
+        c->tgt_cand_valid = 0; c->bad_list_pass = -1;
+        if ((rc = plan_mark_done(p, s))) return rc;
+    }
+    return NBX_OK;
+}
+
 int nbx_leaf_plan_set_cells(nbx_leaf_plan* p, const uint32_t* cell_first_leaf, const uint32_t* cell_leaf_count, size_t n_cells,
                             const uint32_t* far_offsets, const uint32_t* far_cells) {
     if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (int src = plan_needs_structure(p)) return src;
     // every index the two passes will follow, before anything is launched; a refused call leaves the plan and its cells as they were
     if (const char* why = nbx_far::validate_cells(p->n_leaves, cell_first_leaf, cell_leaf_count, n_cells, far_offsets, far_cells))
         return fail(NBX_ERR_INVALID, why);

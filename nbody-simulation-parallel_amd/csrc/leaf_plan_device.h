@@ -425,10 +425,18 @@ inline DevicePlan plan_pointers(char* arena, const Layout& L) {
 // Queue the whole layout on `stream`: the four host arrays in (offsets already checked by the caller: start at 0, non-decreasing --
 // the copies' lengths come from them), every kernel, the summary out into *summary_host (pinned or pageable).  Returns without
 // waiting; the caller synchronises the stream before it reads the summary.  n_leaves >= 1.
+// resident = true: the four arrays are DEVICE pointers (a structure built on the device, octree_device.h) that the kernels read
+// where they are -- no copies, and the Bounds come from counts the builder read back.
 inline hipError_t enqueue_device_plan(const Bounds& b, int dim, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, const uint32_t* list_offsets,
-                                      const uint32_t* list_sources, bool allow_pack, char* arena, const Layout& L, hipStream_t stream, Summary* summary_host) {
+                                      const uint32_t* list_sources, bool allow_pack, char* arena, const Layout& L, hipStream_t stream, Summary* summary_host,
+                                      bool resident = false) {
     using namespace nbx_sort;
-    auto at = [&](size_t off) { return reinterpret_cast<uint32_t*>(arena + off); };
+    auto own = [&](size_t off) { return reinterpret_cast<uint32_t*>(arena + off); };
+    const uint32_t* const d_leaf_offsets = resident ? leaf_offsets : own(L.leaf_offsets);
+    const uint32_t* const d_leaf_bodies = resident ? leaf_bodies : own(L.leaf_bodies);
+    const uint32_t* const d_list_offsets = resident ? list_offsets : own(L.list_offsets);
+    const uint32_t* const d_list_sources = resident ? list_sources : own(L.list_sources);
+    auto at = [&](size_t off) -> uint32_t* { return own(off); };
     const uint32_t nl = (uint32_t)b.n_leaves, slots = (uint32_t)b.slots, n = (uint32_t)b.n;
     const DevicePlan d = plan_pointers(arena, L);
     hipError_t e;
@@ -437,37 +445,39 @@ inline hipError_t enqueue_device_plan(const Bounds& b, int dim, const uint32_t* 
     init.err = kErrNone; init.n_leaves = nl;
     *summary_host = init;   // staged from here: the copy below may be asynchronous
     DP_TRY(hipMemcpyAsync(d.summary, summary_host, sizeof(Summary), hipMemcpyHostToDevice, stream));
-    DP_TRY(hipMemcpyAsync(at(L.leaf_offsets), leaf_offsets, (b.n_leaves + 1) * 4, hipMemcpyHostToDevice, stream));
-    DP_TRY(hipMemcpyAsync(at(L.list_offsets), list_offsets, (b.n_leaves + 1) * 4, hipMemcpyHostToDevice, stream));
-    if (b.slots) DP_TRY(hipMemcpyAsync(at(L.leaf_bodies), leaf_bodies, b.slots * 4, hipMemcpyHostToDevice, stream));
-    if (b.n_list) DP_TRY(hipMemcpyAsync(at(L.list_sources), list_sources, b.n_list * 4, hipMemcpyHostToDevice, stream));
+    if (!resident) {
+        DP_TRY(hipMemcpyAsync(at(L.leaf_offsets), leaf_offsets, (b.n_leaves + 1) * 4, hipMemcpyHostToDevice, stream));
+        DP_TRY(hipMemcpyAsync(at(L.list_offsets), list_offsets, (b.n_leaves + 1) * 4, hipMemcpyHostToDevice, stream));
+        if (b.slots) DP_TRY(hipMemcpyAsync(at(L.leaf_bodies), leaf_bodies, b.slots * 4, hipMemcpyHostToDevice, stream));
+        if (b.n_list) DP_TRY(hipMemcpyAsync(at(L.list_sources), list_sources, b.n_list * 4, hipMemcpyHostToDevice, stream));
+    }
     if (b.n) DP_TRY(hipMemsetAsync(d.body_slot, 0xff, b.n * 4, stream));
     const uint32_t* count_leaves = &d.summary->n_leaves;
     const dim3 blk(256);
     const unsigned leaf_grid = (nl + 255u) / 256u;
     // padded slots
-    hipLaunchKernelGGL(dp_sizes_kernel, dim3(leaf_grid), blk, 0, stream, at(L.leaf_offsets), nl, at(L.groups) /* scratch */, d.summary);
+    hipLaunchKernelGGL(dp_sizes_kernel, dim3(leaf_grid), blk, 0, stream, d_leaf_offsets, nl, at(L.groups) /* scratch */, d.summary);
     DP_TRY(exclusive_scan(at(L.groups), at(L.unit_off), count_leaves, nl, at(L.tile_sums), stream));
     if (slots)
-        hipLaunchKernelGGL(dp_slots_kernel, dim3((slots + 255u) / 256u), blk, 0, stream, at(L.leaf_offsets), at(L.leaf_bodies), at(L.unit_off), nl, slots, n,
+        hipLaunchKernelGGL(dp_slots_kernel, dim3((slots + 255u) / 256u), blk, 0, stream, d_leaf_offsets, d_leaf_bodies, at(L.unit_off), nl, slots, n,
                            d.pslot_body, d.body_slot, d.summary);
     // copy runs: count, offsets, write
-    hipLaunchKernelGGL(dp_runs_kernel<false>, dim3((nl + 3u) / 4u), blk, 0, stream, at(L.list_offsets), at(L.list_sources), at(L.unit_off), nl, at(L.cls_key) /* scratch: counts */,
+    hipLaunchKernelGGL(dp_runs_kernel<false>, dim3((nl + 3u) / 4u), blk, 0, stream, d_list_offsets, d_list_sources, at(L.unit_off), nl, at(L.cls_key) /* scratch: counts */,
                        at(L.stream_units), d.ops, d.summary);
     DP_TRY(exclusive_scan(at(L.cls_key), at(L.op_off), count_leaves, nl, at(L.tile_sums), stream));
-    hipLaunchKernelGGL(dp_runs_kernel<true>, dim3((nl + 3u) / 4u), blk, 0, stream, at(L.list_offsets), at(L.list_sources), at(L.unit_off), nl, at(L.op_off),
+    hipLaunchKernelGGL(dp_runs_kernel<true>, dim3((nl + 3u) / 4u), blk, 0, stream, d_list_offsets, d_list_sources, at(L.unit_off), nl, at(L.op_off),
                        at(L.stream_units), d.ops, d.summary);
     // classes (stable partition by one radix pass), one-leaf workgroups
-    hipLaunchKernelGGL(dp_classify_kernel, dim3(leaf_grid), blk, 0, stream, at(L.leaf_offsets), at(L.op_off), at(L.unit_off), nl, slots, allow_pack ? 1 : 0, d.summary,
+    hipLaunchKernelGGL(dp_classify_kernel, dim3(leaf_grid), blk, 0, stream, d_leaf_offsets, at(L.op_off), at(L.unit_off), nl, slots, allow_pack ? 1 : 0, d.summary,
                        at(L.cls_key), at(L.leaf_id), at(L.groups));
     DP_TRY(radix_pass(at(L.cls_key), at(L.leaf_id), at(L.cls_key2), at(L.order), count_leaves, nl, 0, at(L.hist), stream));
     const uint32_t hist_tiles = sort_tiles(nl);
     DP_TRY(exclusive_scan(at(L.groups), at(L.blk_base), count_leaves, nl, at(L.tile_sums), stream));
     const unsigned windows_max = (unsigned)(b.n_leaves / 32 + kPackClasses + 1);   // >= 32 leaves to a full window in every class
-    hipLaunchKernelGGL(dp_pack_kernel, dim3(windows_max), dim3(128), 0, stream, at(L.leaf_offsets), at(L.op_off), at(L.unit_off), at(L.stream_units), at(L.order),
+    hipLaunchKernelGGL(dp_pack_kernel, dim3(windows_max), dim3(128), 0, stream, d_leaf_offsets, at(L.op_off), at(L.unit_off), at(L.stream_units), at(L.order),
                        at(L.hist), hist_tiles, d.subs, reinterpret_cast<PackBlock*>(arena + L.packs_tmp), d.summary);
     static const PieceCut cuts = best_cuts();
-    hipLaunchKernelGGL(dp_blocks_kernel, dim3(leaf_grid), blk, 0, stream, at(L.leaf_offsets), at(L.op_off), at(L.unit_off), at(L.stream_units), at(L.groups),
+    hipLaunchKernelGGL(dp_blocks_kernel, dim3(leaf_grid), blk, 0, stream, d_leaf_offsets, at(L.op_off), at(L.unit_off), at(L.stream_units), at(L.groups),
                        at(L.blk_base), nl, cuts, reinterpret_cast<LeafBlock*>(arena + L.blocks_tmp), d.summary);
     // launch order
     const unsigned items_max = (unsigned)b.items_max();

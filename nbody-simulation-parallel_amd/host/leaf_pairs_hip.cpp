@@ -125,6 +125,60 @@ float LeafPairSimulationHip<D>::back_to_back_ms(LeafLaw law, int reps) {
 template class LeafPairSimulationHip<2>;
 template class LeafPairSimulationHip<3>;
 
+int barnes_hut_hip_depth(std::size_t n_bodies, int dim) {
+    int depth = 0;
+    while (depth < 10 && static_cast<double>(n_bodies) / std::pow(2.0, depth * dim) > 16.0) ++depth;
+    return depth;
+}
+
+namespace {
+// a context holding the bodies and a plan with the octree built from them; both destroyed on every way out
+template <int D>
+struct OctreeOnDevice {
+    nbx_ctx* ctx = nullptr;
+    nbx_leaf_plan* plan = nullptr;
+    OctreeOnDevice(const std::vector<Body<D>>& bodies, double theta, int depth, const char* where) {
+        const int device = leaf_device();
+        int rc = nbx_ctx_create(&ctx, device, D, bodies.size(), 1, 0);
+        if (!rc) rc = nbx_ctx_upload_bodies(ctx, bodies.data(), sizeof(Body<D>));
+        if (!rc) rc = nbx_leaf_plan_create_octree(&plan, ctx, depth > 0 ? depth : barnes_hut_hip_depth(bodies.size(), D), theta);
+        if (rc != NBX_OK) {
+            nbx_leaf_plan_destroy(plan);
+            nbx_ctx_destroy(ctx);
+            raise_leaf(where, rc);
+        }
+    }
+    ~OctreeOnDevice() {
+        nbx_leaf_plan_destroy(plan);   // before the context, as in LeafPairSimulationHip
+        nbx_ctx_destroy(ctx);
+    }
+};
+}  // namespace
+
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta, int depth) {
+    std::vector<Vector<D>> forces(bodies.size());
+    if (bodies.empty()) return forces;
+    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_n_body");
+    const int rc = nbx_leaf_plan_forces_ctx(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, reinterpret_cast<double*>(forces.data()), nullptr);
+    if (rc != NBX_OK) raise_leaf("barnes_hut_hip_n_body", rc);
+    return forces;
+}
+
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every) {
+    if (bodies.empty()) return;
+    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_steps");
+    int rc = nbx_leaf_plan_step_octree(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, dt, nsteps, rebuild_every);
+    if (!rc) rc = nbx_ctx_download_bodies(tree.ctx, bodies.data(), sizeof(Body<D>));
+    if (rc != NBX_OK) raise_leaf("barnes_hut_hip_steps", rc);
+}
+
+template std::vector<Vector<2>> barnes_hut_hip_n_body<2>(const std::vector<Body<2>>&, double, int);
+template std::vector<Vector<3>> barnes_hut_hip_n_body<3>(const std::vector<Body<3>>&, double, int);
+template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int);
+template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int);
+
 template <int D>
 LeafLists build_uniform_leaves(const std::vector<Body<D>>& bodies, int depth) {
     LeafLists L;

@@ -78,6 +78,19 @@ LeafLists build_uniform_leaves(const std::vector<Body<D>>& bodies, int depth);
 template <int D>
 LeafLists build_octree_cells(const std::vector<Body<D>>& bodies, int depth, double theta);
 
+// Barnes-Hut with the tree built ON THE DEVICE, in the shape of the reference's barnes_hut_seq_n_body (methods.h:47): bodies in,
+// forces out, a new tree per call (methods.cpp:377-401).  The bodies go to a context, the fixed-depth octree, its near and far
+// lists and the plan's layout are made there (nbx_leaf_plan_create_octree), one evaluation under the tree-leaf law with the
+// reference's G follows, and the forces come back.  depth = 0 picks the smallest depth with at most 16 bodies per cell on
+// average (barnes_hut_hip_depth), capped at 10.  Throws std::runtime_error on failure; no CPU fallback.
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta = 0.5, int depth = 0);
+int barnes_hut_hip_depth(std::size_t n_bodies, int dim);
+// nsteps x { rebuild the tree when step % rebuild_every == 0; forces; update_body_velocities; update_body_positions } on the device
+// (nbx_leaf_plan_step_octree), the bodies brought back at the end.
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every = 1);
+
 // kernel time of the most recent leaf_pair_direct_forces_hip call on this thread (ms)
 float last_leaf_pair_kernel_ms();
 

@@ -50,6 +50,8 @@ struct Options {
     std::string law = "reference";  // --law reference|newton: pair law of the stepping loop (newton: extension, needs --softening)
     double softening = 0.0;         // --softening eps: Plummer-softened law in the stepping loop (extension; 0 = reference law)
     std::vector<int> devices;       // --gpus / --devices: shard the HIP rows over these GPUs (one process)
+    double theta = 0.5;             // --theta: opening angle of the `-m t` row (methods.h:47's default)
+    int depth = 0;                  // --depth: octree depth of the `-m t` row (0: at most 16 bodies per cell on average)
     double refine = -1.0;           // --refine tol: per-body relative tolerance of the HIP rows (mixed mode); 0 = plain fp32; < 0: library default (1e-5)
 };
 
@@ -265,6 +267,35 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
         out << std::endl;
     }
 
+    // Barnes-Hut with the octree built on the device: `-m t`.  The whole call is timed, as the reference times barnes_hut_seq_n_body
+    // (a new tree per call, methods.cpp:377-401): upload, tree, lists, layout, moments, near and far pass, forces back.
+    if (m.find('t') != std::string::npos) {
+        const int depth = opt.depth > 0 ? opt.depth : barnes_hut_hip_depth(static_cast<std::size_t>(n), D);
+        out << "Barnes-Hut on HIP (octree of depth " << depth << " built on the device, theta " << opt.theta << "):" << std::endl;
+        Forces forces;
+        const long long us = safely_execute(log, "BarnesHut_HIP", [&] { forces = barnes_hut_hip_n_body<D>(bodies, opt.theta, depth); return 0; });
+        if (us >= 0) {
+            const double seconds = static_cast<double>(us) / 1e6;
+            csv << "BarnesHut_HIP," << n << "," << D;
+            write_time(csv, seconds);
+            if (opt.accuracy) csv << "," << std::fixed << std::setprecision(2) << compute_accuracy<D>(forces, reference);
+            csv << std::endl;
+            out << "Time taken: " << seconds << " s" << std::endl;
+            if (opt.accuracy) out << "Accuracy: " << std::to_string(compute_accuracy<D>(forces, reference)) << "%" << std::endl;
+            print_validation_forces<D>(forces, n, log);
+            print_validation_forces<D>(forces, n, std::cout);
+            if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP.f64", forces);
+            if (opt.steps > 0) {
+                std::vector<Body<D>> state = bodies;
+                const long long step_us = safely_execute(log, "BarnesHut_HIP_steps", [&] { barnes_hut_hip_steps<D>(state, opt.theta, depth, opt.dt, opt.steps, 1); return 0; });
+                if (step_us >= 0)
+                    out << "Barnes-Hut on HIP, " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
+                        << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
+            }
+        }
+        out << std::endl;
+    }
+
     // Near-field (leaf-pair direct sums) of the tree codes on the device: `-m p`.  The tree methods themselves are out of
     // scope; this row times the step they would hand to the GPU (FMM_Parlay<D>::p2p_phase, fmm_parlay.cpp:916-1022) on a
     // fixed-depth subdivision with ~64 bodies per leaf and 3^D neighbour lists.
@@ -419,11 +450,14 @@ void usage(const char* argv0) {
               << "  -m, --methods <str> Specify which methods to run (default: all)" << std::endl
               << "                      a=bruteforce (CPU rows + HIP), g=HIP brute force only," << std::endl
               << "                      p=near-field (leaf-pair) direct sums of the tree codes on HIP," << std::endl
+              << "                      t=Barnes-Hut on HIP, the octree built on the device (--theta, --depth)," << std::endl
               << "                      b=barnes-hut, h=hilbert bvh, f=fmm (not built in this tier)" << std::endl
               << "      --seed <int>    Reproducible bodies (default: random_device, like the reference)" << std::endl
               << "      --init <uniform|plummer>  Initial condition (default: uniform)" << std::endl
               << "      --steps <k>     Also run k kick-drift steps on the device" << std::endl
               << "      --dt <t>        Time step for --steps (default: 1)" << std::endl
+              << "      --theta <t>     Opening angle of the Barnes-Hut row of -m t (default: 0.5)" << std::endl
+              << "      --depth <k>     Octree depth of the Barnes-Hut row of -m t, 1..10 (default: at most 16 bodies per cell on average)" << std::endl
               << "      --G <value>     Coupling constant of the stepping loop (default: the reference's 4.471e-21)" << std::endl
               << "      --integrator <kd|kdk> kd = update_body_velocities then update_body_positions per step (default, first order);" << std::endl
               << "                      kdk = the same helpers as a synchronised kick-drift-kick leapfrog (extension, second order)" << std::endl
@@ -470,9 +504,9 @@ int main(int argc, char* argv[]) {
             opt.methods = argv[++i];
             opt.override_bf_limit = opt.methods == "a";
             for (char c : opt.methods)
-                if (std::string("abhfgp").find(c) == std::string::npos) {
+                if (std::string("abhfgpt").find(c) == std::string::npos) {
                     std::cerr << "Error: Invalid method '" << c << "'" << std::endl
-                              << "Valid methods: a=bruteforce, g=hip bruteforce, p=hip near-field sums, b=barnes-hut, h=bvh, f=fmm" << std::endl;
+                              << "Valid methods: a=bruteforce, g=hip bruteforce, p=hip near-field sums, t=hip barnes-hut, b=barnes-hut, h=bvh, f=fmm" << std::endl;
                     return 1;
                 }
         } else if (arg == "--seed" && has_value) {
@@ -481,6 +515,10 @@ int main(int argc, char* argv[]) {
             opt.steps = std::stoi(argv[++i]);
         } else if (arg == "--dt" && has_value) {
             opt.dt = std::stod(argv[++i]);
+        } else if (arg == "--theta" && has_value) {
+            opt.theta = std::stod(argv[++i]);
+        } else if (arg == "--depth" && has_value) {
+            opt.depth = std::stoi(argv[++i]);
         } else if (arg == "--G" && has_value) {
             opt.G = std::stod(argv[++i]);
         } else if (arg == "--energy-every" && has_value) {
@@ -549,7 +587,7 @@ int main(int argc, char* argv[]) {
 
     set_hip_devices(opt.devices);
     if (opt.refine >= 0.0) set_hip_refine(opt.refine);
-    if (opt.methods.empty() || opt.methods.find_first_of("agp") != std::string::npos)
+    if (opt.methods.empty() || opt.methods.find_first_of("agpt") != std::string::npos)
         warm_up_hip();  // device start-up stays out of the timed rows; a missing GPU surfaces in the HIP row itself
     const std::string run_id = get_run_id();
     try {

@@ -1,0 +1,309 @@
+"""GPU: the octree built on the device (nbx_leaf_plan_create_octree, csrc/octree_device.hip) against the host builder
+leaves.octree_cells, which is its specification: the eight arrays word for word, the forces of a plan made from them bit for bit
+against the host-array path (same structure, same planner, same kernels: the tolerance is zero), brute force at theta = 0 within
+the constants of oracle_lib, rebuilds that follow moving bodies, reuse of the plan's blocks, refusals, and the C++ layer and harness.
+"""
+import contextlib
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle_lib import assert_force_parity
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("leaf_offsets", "leaf_bodies", "list_offsets", "list_sources", "cell_first_leaf", "cell_leaf_count", "far_offsets", "far_cells")
+NBX_ERR_INVALID, NBX_ERR_STATE = 1, 5
+
+
+@contextlib.contextmanager
+def planner(which):
+    before = os.environ.get("NBODY_HIP_LEAF_PLANNER")
+    os.environ["NBODY_HIP_LEAF_PLANNER"] = which
+    try:
+        yield
+    finally:
+        if before is None:
+            del os.environ["NBODY_HIP_LEAF_PLANNER"]
+        else:
+            os.environ["NBODY_HIP_LEAF_PLANNER"] = before
+
+
+def clustered(oracle, dim=3):
+    """Two Gaussian blobs of 30,000 bodies each: leaves of hundreds of bodies next to empty octants."""
+    b = oracle.generate(91, 60000, dim)
+    rng = np.random.default_rng(91)
+    scale = float(np.abs(b[:, :dim]).max())
+    b[:30000, :dim] = rng.normal(-0.4 * scale, 0.001 * scale, size=(30000, dim))
+    b[30000:, :dim] = rng.normal(0.3 * scale, 0.05 * scale, size=(30000, dim))
+    return oracle.round_inputs_to_f32(b)
+
+
+def one_point(oracle):
+    b = oracle.round_inputs_to_f32(oracle.generate(92, 1000, 3))
+    b[:, :3] = b[0, :3]
+    return b
+
+
+def assert_same_structure(got, want, what):
+    assert len(got) == len(want) == 8
+    for name, g, w in zip(NAMES, got, want):
+        assert g.dtype == np.uint32 and g.shape == w.shape, f"{what}: {name} has {g.shape}, the host builder {w.shape}"
+        assert np.array_equal(g, w), f"{what}: {name} differs first at {int(np.nonzero(g != w)[0][0])}"
+
+
+def check_word_for_word(nbx, b, dim, depth, theta, what):
+    n = b.shape[0]
+    want = nbx.leaves.octree_cells(b, dim, depth, theta)
+    with nbx.Context(n, dim) as c:
+        c.upload(b)
+        with nbx.LeafPlan.from_octree(c, depth, theta) as plan:
+            got = plan.structure()
+            sizes = plan.structure_sizes()
+    assert_same_structure(got, want, what)
+    assert sizes == (want[0].size - 1, want[3].size, want[4].size, want[7].size)
+    return want
+
+
+CASES = ((20000, 3, 3, 0.5), (20000, 3, 4, 0.7), (20000, 2, 6, 0.5), (4096, 3, 3, 0.0), (5000, 3, 0, 0.5), (1, 3, 4, 0.5))
+
+
+@pytest.mark.parametrize("n,dim,depth,theta", CASES)
+def test_structure_word_for_word(nbx, oracle, n, dim, depth, theta):
+    b = oracle.round_inputs_to_f32(oracle.generate(300 + depth, n, dim))
+    want = check_word_for_word(nbx, b, dim, depth, theta, f"n={n} dim={dim} depth={depth} theta={theta}")
+    if theta == 0.0:
+        assert want[3].size == (want[0].size - 1) ** 2 and want[7].size == 0      # every leaf on every near list
+
+
+def test_structure_of_bodies_at_one_point(nbx, oracle):
+    want = check_word_for_word(nbx, one_point(oracle), 3, 3, 0.5, "1000 bodies at one point")
+    assert want[0].size == 2
+
+
+def test_structure_of_a_clustered_input_at_depth_10(nbx, oracle):
+    b = clustered(oracle)
+    want = check_word_for_word(nbx, b, 3, 10, 0.5, "two blobs, depth 10")
+    assert int(np.diff(want[0].astype(np.int64)).max()) > 256, "no leaf of more than 256 bodies: the input does not test large leaves"
+
+
+def test_structure_at_size(nbx, oracle):
+    b = oracle.round_inputs_to_f32(oracle.generate(77, 1 << 20, 3))
+    check_word_for_word(nbx, b, 3, 5, 0.5, "N = 2^20 depth 5")
+
+
+BIT_CASES = CASES[:3] + ((1 << 20, 3, 5, 0.5),)
+
+
+@pytest.mark.parametrize("n,dim,depth,theta", BIT_CASES)
+def test_same_bits_as_the_host_array_path(nbx, oracle, n, dim, depth, theta):
+    b = oracle.round_inputs_to_f32(oracle.generate(300 + depth if n < (1 << 20) else 77, n, dim))
+    host = nbx.leaves.octree_cells(b, dim, depth, theta)
+    with nbx.Context(n, dim) as c:
+        c.upload(b)
+        with planner("device"):
+            ref = nbx.LeafPlan(n, dim, *host[:4])
+            ref.set_cells(*host[4:])
+        with ref, nbx.LeafPlan.from_octree(c, depth, theta) as plan:
+            assert plan.info() == ref.info()
+            assert plan.cell_info()[:2] == ref.cell_info()[:2]
+            for law in (0, 1, 2):
+                want = ref.forces_ctx(c, law, oracle.G)
+                got = plan.forces_ctx(c, law, oracle.G)
+                assert np.array_equal(got, want), f"law {law}: {int((got != want).any(axis=1).sum())} bodies differ"
+                assert np.array_equal(plan.get_forces(), want)
+                for g, w in zip(plan.cells(), ref.cells()):
+                    assert np.array_equal(g, w)
+            assert plan.time_kernel(1, 2) > 0.0
+
+
+def test_theta_zero_is_brute_force(nbx, oracle):
+    n, dim = 4096, 3
+    b = oracle.round_inputs_to_f32(oracle.generate(303, n, dim))
+    with nbx.Context(n, dim) as c:
+        c.upload(b)
+        with nbx.LeafPlan.from_octree(c, 3, 0.0) as plan:
+            nl, near, nc, far = plan.structure_sizes()
+            assert near == nl * nl and far == 0
+            f = plan.forces_ctx(c, 0, oracle.G)
+    assert_force_parity(f, oracle.brute_force_seq(b), oracle.force_magnitude_sums(b), "octree plan at theta = 0 vs sequential reference")
+
+
+def host_loop(nbx, b0, dim, depth, theta, law, G, dt, steps, rebuild_every):
+    """Per step: bodies down, octree_cells on them (when the step rebuilds), a fresh LeafPlan + set_cells, forces, kick_drift."""
+    n = b0.shape[0]
+    cur = b0.copy()
+    structures = []
+    with nbx.Context(n, dim) as c, planner("device"):
+        c.upload(b0)
+        plan = None
+        for k in range(steps):
+            if plan is None or (rebuild_every > 0 and k % rebuild_every == 0):
+                if plan is not None:
+                    plan.close()
+                c.download(cur)
+                s = nbx.leaves.octree_cells(cur, dim, depth, theta)
+                structures.append(s)
+                plan = nbx.LeafPlan(n, dim, *s[:4])
+                plan.set_cells(*s[4:])
+            plan.forces_ctx(c, law, G, fetch=False)
+            plan.kick_drift(c, dt)
+        c.download(cur)
+        plan.close()
+    return cur, structures
+
+
+def test_rebuild_follows_the_bodies(nbx, oracle):
+    n, dim, depth, theta, dt, steps = 20000, 3, 4, 0.5, 1.5, 4
+    law, G = nbx.LAW_TREE_LEAF, oracle.G * 1e26
+    b0 = oracle.round_inputs_to_f32(oracle.generate(304, n, dim))
+    b0[:, dim:2 * dim] *= 1000.0
+    for every in (1, 2):
+        want, structures = host_loop(nbx, b0, dim, depth, theta, law, G, dt, steps, every)
+        got = b0.copy()
+        with nbx.Context(n, dim) as c:
+            c.upload(b0)
+            with nbx.LeafPlan.from_octree(c, depth, theta) as plan:
+                plan.step_octree(c, law, G, dt, steps, every)
+                c.download(got)
+                last = plan.structure()
+        assert np.array_equal(got, want), f"bodies after {steps} steps rebuilding every {every}"
+        assert_same_structure(last, structures[-1], f"last structure, rebuilding every {every}")
+        assert not np.array_equal(structures[-1][1], structures[0][1]), "the bodies did not change leaves: the test shows nothing"
+    # rebuild_every = 0 is nbx_leaf_plan_step
+    ga, gb = b0.copy(), b0.copy()
+    with nbx.Context(n, dim) as ca, nbx.Context(n, dim) as cb:
+        ca.upload(b0); cb.upload(b0)
+        with nbx.LeafPlan.from_octree(ca, depth, theta) as pa, nbx.LeafPlan.from_octree(cb, depth, theta) as pb:
+            pa.step_octree(ca, law, G, dt, steps, 0)
+            pb.step(cb, law, G, dt, steps)
+            ca.download(ga); cb.download(gb)
+            assert np.array_equal(ga, gb)
+            assert np.array_equal(pa.get_forces(), pb.get_forces())
+    assert not np.array_equal(ga[:, :dim], b0[:, :dim])
+
+
+def test_determinism_and_reuse(nbx, oracle):
+    n, dim, depth = 20000, 3, 4
+    b = oracle.round_inputs_to_f32(oracle.generate(305, n, dim))
+    wide, narrow = nbx.leaves.octree_cells(b, dim, depth, 0.9), nbx.leaves.octree_cells(b, dim, depth, 0.3)
+    assert narrow[3].size > 4 * wide[3].size, "the two list volumes are too close to test reuse"
+    with nbx.Context(n, dim) as c:
+        c.upload(b)
+        with nbx.LeafPlan.from_octree(c, depth, 0.9) as pa, nbx.LeafPlan.from_octree(c, depth, 0.9) as pb:
+            first = pa.structure()
+            assert_same_structure(pb.structure(), first, "a second build")
+            assert_same_structure(first, wide, "theta 0.9")
+            want = pa.forces_ctx(c, 1, oracle.G)
+            pa.rebuild(c)
+            assert_same_structure(pa.structure(), wide, "theta 0.9 rebuilt")
+            assert np.array_equal(pa.forces_ctx(c, 1, oracle.G), want)
+        # a much larger structure takes the blocks the small ones parked, and a small one comes after it
+        with nbx.LeafPlan.from_octree(c, depth, 0.3) as pc:
+            assert_same_structure(pc.structure(), narrow, "theta 0.3 after theta 0.9")
+            pc.rebuild(c)
+            assert_same_structure(pc.structure(), narrow, "theta 0.3 rebuilt")
+        with nbx.LeafPlan.from_octree(c, depth, 0.9) as pd:
+            assert_same_structure(pd.structure(), wide, "theta 0.9 after theta 0.3")
+            assert np.array_equal(pd.forces_ctx(c, 1, oracle.G), want)
+        # the same plan across a change of list volume: the bodies contract to a tenth (longer near lists per leaf do not follow,
+        # but every array changes size), then come back
+        small = b.copy()
+        small[: n // 2, :dim] *= 0.01
+        small = oracle.round_inputs_to_f32(small)
+        with nbx.LeafPlan.from_octree(c, depth, 0.5) as pe:
+            c.upload(small)
+            pe.rebuild(c)
+            assert_same_structure(pe.structure(), nbx.leaves.octree_cells(small, dim, depth, 0.5), "rebuilt on contracted bodies")
+            c.upload(b)
+            pe.rebuild(c)
+            assert_same_structure(pe.structure(), nbx.leaves.octree_cells(b, dim, depth, 0.5), "rebuilt on the first bodies")
+
+
+def test_refusals(nbx, oracle):
+    n, dim = 5000, 3
+    b = oracle.round_inputs_to_f32(oracle.generate(306, n, dim))
+    want = nbx.leaves.octree_cells(b, dim, 3, 0.5)
+
+    def refused(status, make):
+        with pytest.raises(nbx.NbxError) as e:
+            make()
+        assert e.value.status == status, str(e.value)
+
+    def valid(c):
+        with nbx.LeafPlan.from_octree(c, 3, 0.5) as plan:
+            assert_same_structure(plan.structure(), want, "a valid build after a refusal")
+
+    with nbx.Context(n, dim) as c:
+        refused(NBX_ERR_STATE, lambda: nbx.LeafPlan.from_octree(c, 3, 0.5))          # nothing uploaded yet
+        c.upload(b)
+        valid(c)
+        for depth, theta in ((11, 0.5), (-1, 0.5), (3, -0.1), (3, float("nan")), (3, float("inf"))):
+            refused(NBX_ERR_INVALID, lambda: nbx.LeafPlan.from_octree(c, depth, theta))
+            valid(c)
+        with nbx.Context(n, dim, 0, 2, 0) as two:
+            refused(NBX_ERR_INVALID, lambda: nbx.LeafPlan.from_octree(two, 3, 0.5))
+        valid(c)
+        with nbx.LeafPlan(n, dim, *want[:4]) as host_made:
+            host_made.set_cells(*want[4:])
+            refused(NBX_ERR_STATE, lambda: host_made.rebuild(c))
+            refused(NBX_ERR_STATE, lambda: host_made.structure())
+            refused(NBX_ERR_STATE, lambda: host_made.step_octree(c, 1, oracle.G, 1.0, 1, 1))
+        valid(c)
+        # a coordinate that is not a number: no plan, and the context takes finite bodies afterwards
+        bad = b.copy()
+        bad[n // 2, 1] = float("nan")
+        try:
+            c.upload(bad)
+        except nbx.NbxError:
+            pytest.fail("the context refused the upload: the builder's own check was not reached")
+        refused(NBX_ERR_INVALID, lambda: nbx.LeafPlan.from_octree(c, 3, 0.5))
+        c.upload(b)
+        valid(c)
+        # the same through a rebuild: refused, the plan holds nothing until a rebuild succeeds
+        with nbx.LeafPlan.from_octree(c, 3, 0.5) as plan:
+            c.upload(bad)
+            refused(NBX_ERR_INVALID, lambda: plan.rebuild(c))
+            refused(NBX_ERR_STATE, lambda: plan.forces_ctx(c, 1, oracle.G))
+            c.upload(b)
+            plan.rebuild(c)
+            assert_same_structure(plan.structure(), want, "rebuilt after a refused rebuild")
+
+
+def test_cpp_layer_and_harness(nbx, oracle, tmp_path):
+    """barnes_hut_hip_n_body<3> (a small program built here) gives the forces of the Python octree plan bit for bit; nbody_sim -m t
+    writes a BarnesHut_HIP row with an accuracy value."""
+    n, dim, theta, depth = 20000, 3, 0.5, 4
+    b = oracle.round_inputs_to_f32(oracle.generate(307, n, dim))
+    pkg = os.path.join(ROOT, "nbody-simulation-parallel_amd")
+    exe = str(tmp_path / "octree_cpp_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "host"),
+                    os.path.join(ROOT, "tests", "octree_cpp_check.cpp"), os.path.join(pkg, "host", "leaf_pairs_hip.cpp"), "-o", exe,
+                    "-L" + pkg, "-lnbody_hip", "-Wl,-rpath," + pkg], check=True, capture_output=True, text=True)
+    bodies = str(tmp_path / "bodies.f64")
+    np.ascontiguousarray(b).tofile(bodies)
+    out = str(tmp_path / "forces.f64")
+    p = subprocess.run([exe, bodies, str(n), repr(theta), str(depth), out], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    with nbx.Context(n, dim) as c:
+        c.upload(b)
+        with nbx.LeafPlan.from_octree(c, depth, theta) as plan:
+            f = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)
+        # depth = 0 picks the smallest depth with at most 16 bodies per cell on average: 4 for 20,000 bodies in 3D (8^4 = 4096 cells)
+        p = subprocess.run([exe, bodies, str(n), repr(theta), "0", out + ".auto"], capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stdout + p.stderr
+    assert np.array_equal(np.fromfile(out).reshape(n, dim), f)
+    assert np.array_equal(np.fromfile(out + ".auto").reshape(n, dim), f)
+    sim = os.path.join(ROOT, "nbody_sim")
+    assert os.path.exists(sim)
+    p = subprocess.run([sim, "-N", "20000", "-m", "t", "-a", "1", "--theta", "0.3"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    found = [os.path.join(d, f_) for d, _, files in os.walk(tmp_path) for f_ in files if f_.endswith(".csv")]
+    rows = [line.strip().split(",") for path in found for line in open(path) if line.startswith("BarnesHut_HIP")]
+    assert len(rows) == 1, p.stdout + p.stderr
+    accuracy = float(rows[0][-1])
+    print(f"\nBarnesHut_HIP row: {rows[0]}; accuracy against the brute-force forces {accuracy} %")
+    assert math.isfinite(accuracy) and 0.0 <= accuracy <= 100.0
