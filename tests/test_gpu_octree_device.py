@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import octree_inputs
 from oracle_lib import assert_force_parity
 
 pytestmark = pytest.mark.gpu
@@ -33,19 +34,11 @@ def planner(which):
 
 
 def clustered(oracle, dim=3):
-    """Two Gaussian blobs of 30,000 bodies each: leaves of hundreds of bodies next to empty octants."""
-    b = oracle.generate(91, 60000, dim)
-    rng = np.random.default_rng(91)
-    scale = float(np.abs(b[:, :dim]).max())
-    b[:30000, :dim] = rng.normal(-0.4 * scale, 0.001 * scale, size=(30000, dim))
-    b[30000:, :dim] = rng.normal(0.3 * scale, 0.05 * scale, size=(30000, dim))
-    return oracle.round_inputs_to_f32(b)
+    return octree_inputs.clustered(oracle, dim, 60000, 91)
 
 
 def one_point(oracle):
-    b = oracle.round_inputs_to_f32(oracle.generate(92, 1000, 3))
-    b[:, :3] = b[0, :3]
-    return b
+    return octree_inputs.one_point(oracle, 3, 1000, 92)
 
 
 def assert_same_structure(got, want, what):
@@ -95,7 +88,8 @@ def test_structure_at_size(nbx, oracle):
     check_word_for_word(nbx, b, 3, 5, 0.5, "N = 2^20 depth 5")
 
 
-BIT_CASES = CASES[:3] + ((1 << 20, 3, 5, 0.5),)
+# ... and key sorts of an odd number of passes: 2D depth 4 (8 bits, 1), 3D depth 6 (18 bits, 3), 3D depth 2 (6 bits, 1)
+BIT_CASES = CASES[:3] + ((1 << 20, 3, 5, 0.5), (20000, 2, 4, 0.5), (20000, 3, 6, 0.5), (20000, 3, 2, 0.5))
 
 
 @pytest.mark.parametrize("n,dim,depth,theta", BIT_CASES)
@@ -186,6 +180,32 @@ def test_rebuild_follows_the_bodies(nbx, oracle):
     assert not np.array_equal(ga[:, :dim], b0[:, :dim])
 
 
+@pytest.mark.parametrize("law_name", ("LAW_TREE_LEAF", "LAW_FMM_P2P"))
+@pytest.mark.parametrize("dim,depth", ((2, 4), (3, 6)))
+def test_rebuild_schedule_that_does_not_divide_the_steps(nbx, oracle, dim, depth, law_name):
+    """7 steps rebuilding every 3 (at steps 0, 3 and 6: nbx_leaf_plan_step_octree rebuilds when step % rebuild_every == 0, steps
+    counted from 0, as host_loop does) and every 10 (once, at step 0), with a key sort of 1 pass (2D depth 4) and of 3 (3D depth 6)."""
+    n, theta, dt, steps = 20000, 0.5, 1.5, 7
+    law, G = getattr(nbx, law_name), oracle.G * 1e26
+    b0 = oracle.round_inputs_to_f32(oracle.generate(308 + dim, n, dim))
+    b0[:, dim:2 * dim] *= 1000.0
+    for every, builds in ((3, 3), (10, 1)):
+        want, structures = host_loop(nbx, b0, dim, depth, theta, law, G, dt, steps, every)
+        assert len(structures) == builds
+        got = b0.copy()
+        with nbx.Context(n, dim) as c:
+            c.upload(b0)
+            with nbx.LeafPlan.from_octree(c, depth, theta) as plan:
+                plan.step_octree(c, law, G, dt, steps, every)
+                c.download(got)
+                last = plan.structure()
+        assert np.array_equal(got, want), f"bodies after {steps} steps rebuilding every {every}: {int((got != want).any(axis=1).sum())} differ"
+        assert_same_structure(last, structures[-1], f"last structure, rebuilding every {every}")
+        assert not np.array_equal(got[:, :dim], b0[:, :dim])
+        if builds > 1:
+            assert not np.array_equal(structures[-1][1], structures[0][1]), "the bodies did not change leaves: the test shows nothing"
+
+
 def test_determinism_and_reuse(nbx, oracle):
     n, dim, depth = 20000, 3, 4
     b = oracle.round_inputs_to_f32(oracle.generate(305, n, dim))
@@ -274,8 +294,8 @@ def test_refusals(nbx, oracle):
 
 
 def test_cpp_layer_and_harness(nbx, oracle, tmp_path):
-    """barnes_hut_hip_n_body<3> (a small program built here) gives the forces of the Python octree plan bit for bit; nbody_sim -m t
-    writes a BarnesHut_HIP row with an accuracy value."""
+    """barnes_hut_hip_n_body<3> and <2> (a small program built here) give the forces of the Python octree plan bit for bit,
+    barnes_hut_hip_steps<2> and <3> the bodies of LeafPlan.step_octree; nbody_sim -m t writes a BarnesHut_HIP row with an accuracy value."""
     n, dim, theta, depth = 20000, 3, 0.5, 4
     b = oracle.round_inputs_to_f32(oracle.generate(307, n, dim))
     pkg = os.path.join(ROOT, "nbody-simulation-parallel_amd")
@@ -286,17 +306,38 @@ def test_cpp_layer_and_harness(nbx, oracle, tmp_path):
     bodies = str(tmp_path / "bodies.f64")
     np.ascontiguousarray(b).tofile(bodies)
     out = str(tmp_path / "forces.f64")
-    p = subprocess.run([exe, bodies, str(n), repr(theta), str(depth), out], capture_output=True, text=True, timeout=120)
+    p = subprocess.run([exe, "3", bodies, str(n), str(depth), repr(theta), out], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout + p.stderr
     with nbx.Context(n, dim) as c:
         c.upload(b)
         with nbx.LeafPlan.from_octree(c, depth, theta) as plan:
             f = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)
         # depth = 0 picks the smallest depth with at most 16 bodies per cell on average: 4 for 20,000 bodies in 3D (8^4 = 4096 cells)
-        p = subprocess.run([exe, bodies, str(n), repr(theta), "0", out + ".auto"], capture_output=True, text=True, timeout=120)
+        p = subprocess.run([exe, "3", bodies, str(n), "0", repr(theta), out + ".auto"], capture_output=True, text=True, timeout=120)
         assert p.returncode == 0, p.stdout + p.stderr
     assert np.array_equal(np.fromfile(out).reshape(n, dim), f)
     assert np.array_equal(np.fromfile(out + ".auto").reshape(n, dim), f)
+    # the 2D instance (depth 4: a key sort of one pass), and the step loops of both: 5 steps rebuilding every 2 (at 0, 2 and 4)
+    for d, dep in ((2, 4), (3, 4)):
+        bd = oracle.round_inputs_to_f32(oracle.generate(311 + d, n, d))
+        bd[:, d:2 * d] *= 1000.0
+        path, res = str(tmp_path / f"bodies{d}.f64"), str(tmp_path / f"out{d}.f64")
+        np.ascontiguousarray(bd).tofile(path)
+        stepped = bd.copy()
+        with nbx.Context(n, d) as c:
+            c.upload(bd)
+            with nbx.LeafPlan.from_octree(c, dep, theta) as plan:
+                fd = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)
+                plan.step_octree(c, nbx.LAW_TREE_LEAF, oracle.G, 1.5, 5, 2)
+                c.download(stepped)
+        assert not np.array_equal(stepped[:, :d], bd[:, :d])
+        if d == 2:
+            p = subprocess.run([exe, "2", path, str(n), str(dep), repr(theta), res], capture_output=True, text=True, timeout=120)
+            assert p.returncode == 0, p.stdout + p.stderr
+            assert np.array_equal(np.fromfile(res).reshape(n, d), fd), "barnes_hut_hip_n_body<2>"
+        p = subprocess.run([exe, str(d), path, str(n), str(dep), repr(theta), res + ".steps", "steps", "1.5", "5", "2"], capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stdout + p.stderr
+        assert np.array_equal(np.fromfile(res + ".steps").reshape(n, 2 * d + 1), stepped), f"barnes_hut_hip_steps<{d}>"
     sim = os.path.join(ROOT, "nbody_sim")
     assert os.path.exists(sim)
     p = subprocess.run([sim, "-N", "20000", "-m", "t", "-a", "1", "--theta", "0.3"], cwd=tmp_path, capture_output=True, text=True, timeout=300)

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import octree_inputs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -58,19 +60,9 @@ def test_keys_of_random_bodies(nbx, key_check, tmp_path, dim, depth):
 @pytest.mark.parametrize("dim,depth", ((2, 5), (3, 4), (3, 10)))
 def test_keys_on_cell_boundaries_and_box_faces(nbx, key_check, tmp_path, dim, depth):
     """Bodies exactly on the grid planes of the root box (and one ulp to either side), and on the faces of the bounding box."""
-    g = 1 << depth
-    corners = np.array([[1.0] * dim, [1.0e7] * dim])
-    _, origin, side = host_cells(corners, dim, depth)
-    rng = np.random.default_rng(7 * dim + depth)
-    k = rng.integers(1, g, (3000, dim))
-    on = origin + side * (k / g)
-    on = np.clip(on, 1.0, 1.0e7)                                     # the two corners keep the box as it is
-    pos = np.concatenate([corners, on, np.nextafter(on, -np.inf), np.nextafter(on, np.inf)])
-    faces = rng.uniform(1.0, 1.0e7, (600, dim))
-    for d in range(dim):
-        faces[200 * d:200 * d + 100, d] = 1.0                        # on the lower face of the bounding box ...
-        faces[200 * d + 100:200 * d + 200, d] = 1.0e7                # ... and on the upper one
-    pos = np.concatenate([pos, faces[:200 * dim]])
+    pos = octree_inputs.plane_positions(dim, depth, 7 * dim + depth)
+    assert pos.shape[0] == 2 + 3 * 3000 + 200 * dim
+    assert octree_inputs.share_on_grid_planes(pos, depth) >= 1.0 / 3.0, "the input misses the planes it is made for"
     compare(nbx, key_check, tmp_path, pos, dim, depth, f"boundaries dim {dim} depth {depth}")
 
 
@@ -83,6 +75,34 @@ def test_keys_of_a_single_point(nbx, key_check, tmp_path, dim):
             compare(nbx, key_check, tmp_path, pos, dim, depth, f"{n} bodies at one point, depth {depth}")
     compare(nbx, key_check, tmp_path, np.zeros((10, dim)), dim, 3, "bodies at the origin")
     compare(nbx, key_check, tmp_path, -np.abs(np.random.default_rng(5).normal(0, 1e-3, (300, dim))), dim, 6, "small negative coordinates")
+
+
+GEOMETRY = [(name, dim, n, seed, depth) for name, dim, n, seed, depths in octree_inputs.GEOMETRY_CASES for depth in depths]
+
+
+@pytest.mark.parametrize("name,dim,n,seed,depth", GEOMETRY, ids=[f"{c[0]}-{c[1]}d-depth{c[4]}" for c in GEOMETRY])
+def test_keys_of_every_named_input(nbx, oracle, key_check, tmp_path, name, dim, n, seed, depth):
+    """The CPU twin of tests/test_gpu_octree_sweep.py's geometry cases: the same bodies at the same depths through the g++ build of
+    the shared header.  A device mismatch on one of them that this test does not show lies in the device kernels, not the header."""
+    b = octree_inputs.GENERATORS[name](oracle, dim, n, seed, depth)
+    assert b.shape[1] == 2 * dim + 1 and abs(b.shape[0] - n) <= 2 * dim + 2
+    if name in ("planes", "lattice"):
+        assert octree_inputs.share_on_grid_planes(b[:, :dim], depth) >= 1.0 / 3.0, "the input misses the planes it is made for"
+    cell = compare(nbx, key_check, tmp_path, b[:, :dim], dim, depth, f"{name} dim {dim} depth {depth}")
+    if name in ("one_point", "denormal"):
+        assert np.unique(cell, axis=0).shape[0] == 1                 # everything in one leaf
+    if name in ("slab", "line"):
+        assert np.unique(cell[:, 2]).size == 1 and np.unique(cell[:, 0]).size > 1
+
+
+def test_size_cases_put_leaf_counts_on_the_wave_edges(nbx, oracle):
+    """The body counts of the GPU size sweep (octree_inputs.SIZES, with their seeds) give, by the host builder alone, leaf counts
+    that are 0, 1 and 63 mod 64: a full last wave of the walk, a wave of one lane, and a wave one lane short."""
+    counts = {(n, depth): octree_inputs.leaf_count(nbx.leaves, octree_inputs.size_case(oracle, n), 3, depth)
+              for n in octree_inputs.SIZES for depth in octree_inputs.SIZE_DEPTHS}
+    print("\n" + "\n".join(f"n {n} depth {depth}: n_leaves {nl} (mod 64: {nl % 64}, mod 256: {nl % 256})" for (n, depth), nl in counts.items()))
+    assert {nl % 64 for nl in counts.values()} >= {0, 1, 63}
+    assert {nl % 256 for nl in counts.values()} >= {0, 1, 255}
 
 
 def test_octree_entries_reject_null_arguments(nbx):
