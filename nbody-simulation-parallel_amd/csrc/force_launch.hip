@@ -25,6 +25,7 @@ struct Table {
         const KernelVariant* a = kernel_variants(&n);
         for (int i = 0; i < n; ++i) v.push_back(a[i]);
         v.push_back(sym_kernel_variant());
+        v.push_back(sym_dpp_kernel_variant());   // comparator: after everything else, no existing index moves
         for (size_t i = 0; i < v.size(); ++i) {
             if (std::strcmp(v[i].name, NBX_DEFAULT_VARIANT) == 0) def = (int)i;
             if (std::strcmp(v[i].name, NBX_DEFAULT_EXACT_VARIANT) == 0) def_exact = (int)i;

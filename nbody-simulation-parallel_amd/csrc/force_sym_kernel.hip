@@ -10,8 +10,14 @@
 //   * It takes 64 VISITORS, one per lane: {x, y}, {z, m} and a float2 x 3 reaction accumulator.  One step = the fast
 //     kernel's loop body with the source operands read from the lane's visitor registers instead of an LDS broadcast, plus
 //     the multiply by the home masses and 3 v_pk_fma_f32 into the visitor's accumulator.  Then the visitor and its
-//     accumulator move one lane on (v_mov_b32_dpp wave_ror:1).  After 64 steps every home body has met every visitor and
-//     every visitor is back in its lane.  No LDS broadcast, no barrier and no cross-lane reduction in the pair loop.
+//     accumulator move one lane on.  After 64 steps every home body has met every visitor and every visitor is back in
+//     its lane.  No LDS broadcast, no barrier and no cross-lane reduction in the pair loop.
+//   * The rotation (template parameter ROT).  The accumulator changes every step and moves by v_mov_b32_dpp wave_ror:1
+//     (6 moves per step).  The visitor's {x, y, z, m} never change during a rotation:
+//       kRotLds: the wave writes its 64 visitors once per group into a wave-private LDS buffer and every lane reads the
+//                next step's visitor with one ds_read_b128, issued one step ahead -- the VALU is the saturated pipe, the
+//                LDS pipe is idle.  A wave's LDS operations complete in order and nobody else touches the buffer: no barrier.
+//       kRotDpp: four more DPP moves per step (the comparator sympk3l_t8_w3_dpp: same values, same sums, bit for bit).
 //   * Summation, three levels on both sides:
 //       home:    fp32 over the 64 steps of one visitor group -> fp32 over the <= 4 groups of a chunk -> fp64 (LDS);
 //       visitor: fp32 over 8 steps (32 terms per float2 half) -> fp32 over the 8 such blocks of a rotation, kept in the
@@ -37,6 +43,14 @@ __device__ __forceinline__ float ror1(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0x13C, 0xF, 0xF, false));
 }
 __device__ __forceinline__ void ror1(f2& v) { v.x = ror1(v.x); v.y = ror1(v.y); }
+
+enum { kRotDpp = 0, kRotLds = 1 };   // how the visitor's {x, y, z, m} reach the next lane
+// kRotLds, the wave's buffer.  With delta = +-1 the lanes' move per step, entry k holds the visitor of the lane -k * delta
+// (mod 64), and the lane that starts at entry r = -lane * delta finds the visitor of step t at entry r - t: the direction
+// is in the placement, the loop reads downwards whichever it is.  Entries 64.. repeat entries 0.. so that r + 64 - t needs
+// no wrap inside a block of eight steps: D = 3 keeps all 64 twice (one base update per block, no wrap at all); D = 2
+// keeps 8 (its three workgroups per CU leave no room for more) and wraps the block's base.
+template <int D> struct RotBuf { static constexpr unsigned kEntries = (D == 3) ? 128u : 72u; };
 
 // One step: the lane's PAIRS home pairs against the lane's visitor.  Per home pair, D = 3: v_pk_add x3, v_pk_fma x3
 // (r^2 + bias), v_rcp x2, v_pk_mul (w^2), v_pk_mul x2 (the two masses), v_pk_fma x3 (home), v_pk_fma x3 (visitor) = 16 + 2.
@@ -99,12 +113,14 @@ __device__ __forceinline__ void store_hi_lo(float* __restrict__ hi_plane, float*
 }
 
 // grid = (B super-blocks, S slices), 256 lanes.  acc = [S + K slots][{hi, lo}][D][pad], qsum = [S + K slots][pad].
-template <int D, int QS>
+template <int D, int QS, int ROT>
 __global__ __launch_bounds__(256, 2) void accel_sym3l_kernel(KArgs a) {
     constexpr int PAIRS = 4;
     constexpr unsigned kSumBytes = (unsigned)PAIRS * D * 256u * sizeof(double2);          // home level 3: [PAIRS*D][256] double2
     constexpr unsigned kVisBytes = 4u * kSymChunkGroups * kSymGroup * sizeof(float4);     // visitor level 2: [wave][group][visitor] {x, y, z, Q}
-    __shared__ __attribute__((aligned(16))) char smem[kSumBytes + kVisBytes];
+    constexpr unsigned kRotEntries = RotBuf<D>::kEntries;
+    constexpr unsigned kRotBytes = (ROT == kRotLds) ? 4u * kRotEntries * sizeof(float4) : 0u;   // rotation: [wave][entry] {x, y, z, m}
+    __shared__ __attribute__((aligned(16))) char smem[kSumBytes + kVisBytes + kRotBytes];
     double2* __restrict__ sums = reinterpret_cast<double2*>(smem);
     float4* __restrict__ vbuf = reinterpret_cast<float4*>(smem + kSumBytes);
 
@@ -127,6 +143,9 @@ __global__ __launch_bounds__(256, 2) void accel_sym3l_kernel(KArgs a) {
 
     // after t moves a lane holds the visitor that started (t * delta) lanes further on (mod 64); delta is read off the move itself
     const unsigned delta = ((unsigned)__builtin_amdgcn_update_dpp((int)lane, (int)lane, 0x13C, 0xF, 0xF, false) - lane) & 63u;
+    // kRotLds: the lane's starting entry in its wave's rotation buffer (RotBuf)
+    const unsigned rpos = ((0u - delta) * lane) & 63u;
+    const unsigned vrot = kSumBytes + kVisBytes + ((ROT == kRotLds) ? wave * kRotEntries * (unsigned)sizeof(float4) : 0u);   // bytes into smem
 
     if (sym_clears_last_slot(P, A)) {   // rows nobody else writes (sym_plan.h)
         float* __restrict__ hi = a.acc + (size_t)(P.S + P.K - 1u) * slot_stride;
@@ -182,18 +201,53 @@ __global__ __launch_bounds__(256, 2) void accel_sym3l_kernel(KArgs a) {
                 // cleared here rather than by a branch on the first block: the block loop's body stays one basic block (a branch
                 // made the compiler sink the home sums' arithmetic of all eight steps below it, at 256 VGPRs and spills)
                 vslot[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+                // the group's visitors into the wave's rotation buffer: the last read of the previous group precedes this write
+                // in the wave's LDS queue, and the first read below follows it
+                unsigned roff = 0u;   // bytes into smem (D = 2: into the wave's buffer) of the entry the block's last read takes
+                if (ROT == kRotLds) {
+                    const float4 me = make_float4(vxy.x, vxy.y, vzm.x, vzm.y);
+                    *reinterpret_cast<float4*>(smem + vrot + rpos * 16u) = me;
+                    if (kRotEntries == 128u || rpos < kRotEntries - 64u) *reinterpret_cast<float4*>(smem + vrot + (rpos + 64u) * 16u) = me;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    // block 0 reads steps 1 .. 8 = entries r + 63 .. r + 56
+                    roff = (kRotEntries == 128u) ? vrot + (rpos + 56u) * 16u : ((rpos + 56u) & 63u) * 16u;
+                    asm volatile("" : "+v"(roff));
+                }
                 f2 ax[PAIRS], ay[PAIRS], az[PAIRS];
 #pragma unroll
                 for (int q = 0; q < PAIRS; ++q) ax[q] = ay[q] = az[q] = f2{0.f, 0.f};
 #pragma unroll 1
                 for (unsigned blk = 0; blk < 8u; ++blk) {
                     f2 vax = f2{0.f, 0.f}, vay = f2{0.f, 0.f}, vaz = f2{0.f, 0.f};
+                    // the block's base address stays one register: left to itself the compiler splits it into a per-lane and a
+                    // per-block part and adds them up again in front of every read
+                    const char* rot = smem;
+                    if (ROT == kRotLds) rot = smem + ((kRotEntries == 128u) ? roff : vrot + roff);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        sym_step<D, PAIRS>(vxy, vzm, ix, iy, iz, hm, ax, ay, az, vax, vay, vaz, bias);
-                        ror1(vxy); ror1(vzm); ror1(vax); ror1(vay);
+                        if (ROT == kRotLds) {
+                            // {z, m} stays one register pair (taken apart, m's broadcast costs a v_mov_b32 per step); this is
+                            // also where the wait for the previous step's read lands: behind that step's arithmetic
+                            asm volatile("" : "+v"(vzm));
+                            // the next step's visitor flies while this step computes; the eight reads of a block differ in the
+                            // instruction's immediate offset only.  (The 64th read fetches step 0's visitor again, unused.)
+                            const float4 nv = *reinterpret_cast<const float4*>(rot + (7 - j) * 16);
+                            __builtin_amdgcn_sched_barrier(0);   // issued first: the scheduler would sink it to within 40 cycles of its use
+                            sym_step<D, PAIRS>(vxy, vzm, ix, iy, iz, hm, ax, ay, az, vax, vay, vaz, bias);
+                            vxy = f2{nv.x, nv.y}; vzm = f2{nv.z, nv.w};
+                        } else {
+                            sym_step<D, PAIRS>(vxy, vzm, ix, iy, iz, hm, ax, ay, az, vax, vay, vaz, bias);
+                            ror1(vxy); ror1(vzm);
+                        }
+                        ror1(vax); ror1(vay);
                         if (D == 3) ror1(vaz);
                         __builtin_amdgcn_sched_barrier(0);   // one step at a time: interleaving the unrolled steps only costs registers
+                    }
+                    if (ROT == kRotLds) {   // the next block's eight entries lie below; D = 2's short buffer wraps
+                        roff = (kRotEntries == 128u) ? roff - 128u : (roff - 128u) & 1023u;
+                        asm volatile("" : "+v"(roff));
                     }
                     // visitor level 1 -> level 2, in the wave's slot of the visitor that now sits in this lane
                     const unsigned vid = (lane + (blk + 1u) * 8u * delta) & 63u;
@@ -295,17 +349,23 @@ __global__ __launch_bounds__(256, 2) void accel_sym3l_kernel(KArgs a) {
 }  // namespace
 
 // the table entry of this unit (force_launch.hip appends it to force_kernel.hip's)
-KernelVariant sym_kernel_variant() {
+namespace {
+template <int ROT>
+KernelVariant sym_variant(const char* name) {
     KernelVariant v = {};
-    v.name = "sympk3l_t8_w3";
+    v.name = name;
     v.tpl = 8;
-    v.k2 = accel_sym3l_kernel<2, 0>; v.k3 = accel_sym3l_kernel<3, 0>;
-    v.qs2 = accel_sym3l_kernel<2, 1>; v.qs3 = accel_sym3l_kernel<3, 1>;
+    v.k2 = accel_sym3l_kernel<2, 0, ROT>; v.k3 = accel_sym3l_kernel<3, 0, ROT>;
+    v.qs2 = accel_sym3l_kernel<2, 1, ROT>; v.qs3 = accel_sym3l_kernel<3, 1, ROT>;
     v.fast = 1;
     v.planes = 2;
     v.sym = 1;
     v.stamps = 1;
     return v;
 }
+}  // namespace
+KernelVariant sym_kernel_variant() { return sym_variant<kRotLds>("sympk3l_t8_w3"); }
+// the parent form of the rotation, for the A/B and the identity test: never a default, last in the table
+KernelVariant sym_dpp_kernel_variant() { return sym_variant<kRotDpp>("sympk3l_t8_w3_dpp"); }
 
 }  // namespace nbx

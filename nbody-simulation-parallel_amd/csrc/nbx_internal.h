@@ -171,6 +171,7 @@ struct KernelVariant {
 const KernelVariant* kernel_variants(int* count);
 // force_sym_kernel.hip
 KernelVariant sym_kernel_variant();
+KernelVariant sym_dpp_kernel_variant();   // the same pass with every rotation on DPP moves (comparator, last in the table)
 struct CloseKernels { void (*classify[2])(KArgs); void (*classify_src[2])(KArgs); void (*refine[2])(KArgs); void (*scatter[2])(KArgs); void (*potential[2])(KArgs); void (*potential_soft[2])(KArgs); void (*potential_newton[2])(KArgs);
                       void (*refine_select[2])(KArgs); void (*strict_list[2])(KArgs); void (*refine_fold[2])(KArgs);
                       void (*close_only[2])(KArgs); };  // [0]: D=2, [1]: D=3
