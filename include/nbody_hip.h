@@ -238,6 +238,19 @@ int nbx_leaf_plan_cell_info(nbx_leaf_plan* plan, size_t* n_cells, size_t* far_en
  * NBX_ERR_INVALID: null pointers, a context of several shards or without bodies, depth or theta out of range, a coordinate
  * that is not finite (no plan is made), more than 0xfffffff0 near or far entries.  NBX_ERR_STATE: nothing uploaded yet. */
 int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* ctx, int depth, double theta);
+/* The ADAPTIVE octree: leaves of bounded occupancy, for inputs whose density varies (a Plummer sphere's centre puts thousands of
+ * bodies into one cell of any fixed depth).  Root box, finest cells (at max_depth), Morton keys and body order are those of
+ * nbx_leaf_plan_create_octree(depth = max_depth).  A node is a key prefix at level L <= max_depth.  The root is split when
+ * max_depth >= 1 and (leaf_capacity == 0 or n > leaf_capacity); a node of level L >= 1 exists when it is not empty and its parent
+ * is split; an existing node is a leaf at L == max_depth or, for leaf_capacity > 0, when it holds at most leaf_capacity bodies,
+ * and is split otherwise.  Leaves in Morton order; cells = the existing nodes of levels 1 .. max_depth, level by level (every
+ * leaf is one of them); the walk tests a node against the target leaf's OWN box: accepted when node_side < theta * gap, near
+ * list when it is a leaf that is not accepted, opened otherwise -- so for every leaf the bodies of its near leaves and far cells
+ * number exactly n.  An unsplit root gives one leaf, its near list itself, and no cells.  leaf_capacity = 0 is
+ * nbx_leaf_plan_create_octree(depth = max_depth).  The host builders leaves.adaptive_octree_cells and
+ * build_adaptive_octree_cells<D> make the same eight arrays word for word.  Errors as nbx_leaf_plan_create_octree; a negative
+ * leaf_capacity is NBX_ERR_INVALID.  Every nbx_leaf_plan_* call works on such a plan; a rebuild keeps all three parameters. */
+int nbx_leaf_plan_create_octree_adaptive(nbx_leaf_plan** out, nbx_ctx* ctx, int max_depth, int leaf_capacity, double theta);
 /* Builds the structure again, with the same depth and theta, from the context's current positions.  The plan's device blocks
  * are reused where they fit.  NBX_ERR_STATE for a plan not made by nbx_leaf_plan_create_octree.  After a refused rebuild the
  * plan holds no structure (evaluations return NBX_ERR_STATE) until a rebuild succeeds. */

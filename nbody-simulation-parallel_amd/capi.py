@@ -54,6 +54,7 @@ ABI = [
     ("nbx_leaf_plan_get_cells", _i, [_vp, _vp, _vp]),
     ("nbx_leaf_plan_cell_info", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _pf, _pf]),
     ("nbx_leaf_plan_create_octree", _i, [_c.POINTER(_vp), _vp, _i, _d]),
+    ("nbx_leaf_plan_create_octree_adaptive", _i, [_c.POINTER(_vp), _vp, _i, _i, _d]),
     ("nbx_leaf_plan_rebuild_octree", _i, [_vp, _vp]),
     ("nbx_leaf_plan_structure_sizes", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz)]),
     ("nbx_leaf_plan_get_structure", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -308,6 +309,20 @@ class LeafPlan:
         self.n, self.dim, self.device = int(ctx.n_total), int(ctx.dim), ctx.device
         h = ctypes.c_void_p()
         _check(self.lib, self.lib.nbx_leaf_plan_create_octree(ctypes.byref(h), ctx.h, int(depth), float(theta)), "nbx_leaf_plan_create_octree")
+        self.h = h
+        return self
+
+    @classmethod
+    def from_octree_adaptive(cls, ctx: "Context", max_depth: int, leaf_capacity: int, theta: float) -> "LeafPlan":
+        """An adaptive octree built ON THE DEVICE (nbx_leaf_plan_create_octree_adaptive): leaves of at most `leaf_capacity` bodies
+        down to `max_depth`, the structure leaves.adaptive_octree_cells(bodies, dim, max_depth, leaf_capacity, theta) makes on the
+        host.  leaf_capacity = 0 is from_octree(ctx, max_depth, theta)."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.n, self.dim, self.device = int(ctx.n_total), int(ctx.dim), ctx.device
+        h = ctypes.c_void_p()
+        _check(self.lib, self.lib.nbx_leaf_plan_create_octree_adaptive(ctypes.byref(h), ctx.h, int(max_depth), int(leaf_capacity), float(theta)),
+               "nbx_leaf_plan_create_octree_adaptive")
         self.h = h
         return self
 

@@ -896,6 +896,7 @@ struct nbx_leaf_plan {
     bool octree_built = false;      // ... and its last build went through (a refused rebuild leaves nothing to evaluate)
     int octree_depth = 0;
     double octree_theta = 0.0;
+    size_t octree_capacity = 0;     // > 0: the adaptive tree (nbx_leaf_plan_create_octree_adaptive), octree_depth its max_depth
     char* tree_arena = nullptr;     // the builder's block: the tree, six of the eight structure arrays, scratch
     size_t tree_arena_bytes = 0;
     nbx_octree::TreeLayout tree_layout{};
@@ -1376,7 +1377,11 @@ int plan_build_octree(nbx_leaf_plan* p, nbx_ctx* c) {
     const int dim = p->dim, depth = p->octree_depth;
     const nbx_octree::TreeLayout& T = p->tree_layout;
     if (int rc = plan_fit_arena(p, T.total, &p->tree_arena, &p->tree_arena_bytes)) return rc;
-    NBX_HIP_TRY(nbx_octree::enqueue_build(c->x64, c->pad, p->n, dim, depth, p->octree_theta, p->tree_arena, T, s, &p->counts_host, &p->tree));
+    if (p->octree_capacity)
+        NBX_HIP_TRY(nbx_octree::enqueue_build_adaptive(c->x64, c->pad, p->n, dim, depth, p->octree_capacity, p->octree_theta, p->tree_arena, T, s, &p->counts_host,
+                                                       &p->tree));
+    else
+        NBX_HIP_TRY(nbx_octree::enqueue_build(c->x64, c->pad, p->n, dim, depth, p->octree_theta, p->tree_arena, T, s, &p->counts_host, &p->tree));
     NBX_HIP_TRY(hipStreamSynchronize(s));   // the counts are here; whatever used the plan's blocks before is over
     if (int rc = plan_mark_done(p, s)) return rc;
     const nbx_octree::Counts C = p->counts_host;
@@ -1407,7 +1412,10 @@ int plan_build_octree(nbx_leaf_plan* p, nbx_ctx* c) {
     char* const cells = p->cell_arena;
     uint32_t* const far_cells = reinterpret_cast<uint32_t*>(cells + offs[0]);
     nbx_far::FarBlock* const far_blocks = reinterpret_cast<nbx_far::FarBlock*>(cells + offs[1]);
-    NBX_HIP_TRY(nbx_octree::enqueue_fill(p->n, dim, depth, p->octree_theta, p->tree_arena, T, list_sources, far_cells, s));
+    if (p->octree_capacity)
+        NBX_HIP_TRY(nbx_octree::enqueue_fill_adaptive(p->n, dim, depth, p->octree_capacity, p->octree_theta, p->tree_arena, T, list_sources, far_cells, s));
+    else
+        NBX_HIP_TRY(nbx_octree::enqueue_fill(p->n, dim, depth, p->octree_theta, p->tree_arena, T, list_sources, far_cells, s));
     NBX_HIP_TRY(enqueue_device_plan(b, dim, p->tree.leaf_offsets, p->tree.leaf_bodies, p->tree.list_offsets, list_sources, NBX_LEAF_PACK != 0, p->arena, L, s,
                                     &p->summary_host, true));
     if (nc) NBX_HIP_TRY(nbx_octree::enqueue_far_layout(p->unit_off, C, p->tree_arena, T, far_blocks, cells + offs[6], s));
@@ -1453,11 +1461,9 @@ int plan_check_ctx(const nbx_leaf_plan* p, const nbx_ctx* c) {
     if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
     return NBX_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* c, int depth, double theta) {
+// both octree entry points: leaf_capacity = 0 is the fixed-depth tree
+int create_octree_plan(nbx_leaf_plan** out, nbx_ctx* c, int depth, size_t leaf_capacity, double theta) {
     if (!out) return fail(NBX_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
@@ -1469,8 +1475,8 @@ int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* c, int depth, doub
     nbx_leaf_plan* p = new (std::nothrow) nbx_leaf_plan();
     if (!p) return fail(NBX_ERR_ALLOC, "host allocation failed");
     p->device = c->device; p->dim = c->dim; p->n = c->n_total;
-    p->octree = true; p->octree_depth = depth; p->octree_theta = theta;
-    p->tree_layout = nbx_octree::make_tree_layout(p->n, p->dim, depth);
+    p->octree = true; p->octree_depth = depth; p->octree_theta = theta; p->octree_capacity = leaf_capacity;
+    p->tree_layout = nbx_octree::make_tree_layout(p->n, p->dim, depth, leaf_capacity > 0);
     DeviceScope scope;
     hipError_t e = hipSetDevice(p->device);
     if (e == hipSuccess) e = nbx::take_stream(p->device, &p->stream);
@@ -1481,6 +1487,19 @@ int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* c, int depth, doub
     if (rc) { nbx_leaf_plan_destroy(p); return rc; }
     *out = p;
     return NBX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* c, int depth, double theta) { return create_octree_plan(out, c, depth, 0, theta); }
+
+int nbx_leaf_plan_create_octree_adaptive(nbx_leaf_plan** out, nbx_ctx* c, int max_depth, int leaf_capacity, double theta) {
+    if (leaf_capacity < 0) {
+        if (out) *out = nullptr;
+        return fail(NBX_ERR_INVALID, out ? "leaf_capacity must be >= 0" : "out is null");
+    }
+    return create_octree_plan(out, c, max_depth, (size_t)leaf_capacity, theta);
 }
 
 int nbx_leaf_plan_rebuild_octree(nbx_leaf_plan* p, nbx_ctx* c) {

@@ -18,6 +18,15 @@
 //   walk, filling               ot_walk<true>                                       lexsort / stable argsort of the frontier's output
 //   far layout                  ot_far_blocks, radix passes by far-list length,     leaf_far.h plan_far
 //                               ot_far_deal
+// The ADAPTIVE tree of leaves.adaptive_octree_cells (nbx_leaf_plan_create_octree_adaptive) shares the first two stages, run at
+// max_depth, and everything after the walk; between them (ota_* kernels):
+//   leaf level of every run     per level ot_flags + scan, ota_node_starts,         np.unique(.., return_inverse), count <= capacity
+//                               ota_run_level
+//   leaves                      ota_leaf_flags, scan, ota_leaves                    runs of equal (leaf level, prefix)
+//   existing nodes per level    per level ota_level_flags + scan; ot_level_bases,   np.unique over the leaves of level >= L
+//                               ota_cells (count: a binary search), one radix pass
+//   walk                        ot_walk<FILL, true>: stops at a leaf of any level,  the frontier with lv_leaf and the leaves' own boxes
+//                               accepts_box with the target leaf's own side
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -96,6 +105,24 @@ NBX_OT_HD inline bool accepts(uint32_t q_packed, uint32_t node_packed, int dim, 
     return (double)(1ll << s) < theta * sqrt((double)sum);
 }
 
+// The same test for a target that is a node of ANY level (the adaptive tree): t = the target leaf's cell at its own level, st =
+// max_depth - that level, so its box is [t << st, (t << st) + 2^st) in units of the finest grid.  st = 0 is accepts().
+NBX_OT_HD inline bool accepts_box(uint32_t t_packed, int st, uint32_t node_packed, int dim, int s, double theta) {
+    long long sum = 0;
+    for (int d = 0; d < dim; ++d) {
+        const long long q = (long long)((t_packed >> (10 * d)) & 1023u) << st, blo = (long long)((node_packed >> (10 * d)) & 1023u) << s;
+        long long gap = blo - (q + (1ll << st));
+        const long long other = q - (blo + (1ll << s));
+        gap = gap > other ? gap : other;
+        gap = gap > 0 ? gap : 0;
+        sum += gap * gap;
+    }
+    return (double)(1ll << s) < theta * sqrt((double)sum);
+}
+
+// The adaptive tree's root is split (otherwise: one leaf, no cells).  leaf_capacity = 0: the fixed-depth tree.
+NBX_OT_HD inline bool root_is_split(size_t n, int max_depth, size_t leaf_capacity) { return max_depth >= 1 && (leaf_capacity == 0 || n > leaf_capacity); }
+
 }  // namespace nbx_octree
 
 #ifdef __HIPCC__
@@ -115,7 +142,8 @@ struct Counts {
     unsigned long long far_entries;
     uint32_t far_blocks;             // waves of the far pass (leaf_far.h plan_far)
     uint32_t n;                      // the bodies (the sort's count word)
-    uint32_t pad_[6];
+    uint32_t n_runs;                 // adaptive tree: the non-empty cells of the finest grid (its leaves are unions of them)
+    uint32_t pad_[5];
 };
 static_assert(sizeof(Counts) == 64, "one cache line, copied back whole");
 
@@ -127,10 +155,11 @@ struct TreeLayout {
     size_t rank;                     // [depth + 1][nl_max + 1]: a leaf's node at every level
     size_t cell_first, cell_count, cell_coords, child_first, child_end, cell_key, cell_key2, cell_id, cells_split;
     size_t far_blk_cnt, far_blk_off;
+    size_t run_off, run_keys, run_level, node_at, node_start, leaf_level;   // the adaptive tree only (0 otherwise)
     size_t total;
     size_t nl_max, cells_max;
 };
-TreeLayout make_tree_layout(size_t n, int dim, int depth);
+TreeLayout make_tree_layout(size_t n, int dim, int depth, bool adaptive = false);
 
 struct Tree {                        // device pointers into the tree block, for the plan to keep
     Counts* counts = nullptr;
@@ -149,6 +178,14 @@ hipError_t enqueue_build(const double* x64, size_t pad, size_t n, int dim, int d
 // the filling walk: list_sources[near_entries], far_cells[far_entries]
 hipError_t enqueue_fill(size_t n, int dim, int depth, double theta, char* block, const TreeLayout& L, uint32_t* list_sources, uint32_t* far_cells,
                         hipStream_t s);
+// The ADAPTIVE tree (leaves.adaptive_octree_cells; leaf_capacity > 0, a layout made with adaptive = true): bounding box, keys, sort
+// and finest runs as above at depth = max_depth; then per level the nodes' body counts from the runs' offsets, every run's leaf
+// level, the leaves as runs of equal (level, prefix), the existing nodes per level, and the same walk stopping at a leaf of any
+// level and testing with the target leaf's own box.  Everything downstream (enqueue_far_layout, the plan) is shared.
+hipError_t enqueue_build_adaptive(const double* x64, size_t pad, size_t n, int dim, int max_depth, size_t leaf_capacity, double theta, char* block,
+                                  const TreeLayout& L, hipStream_t s, Counts* counts_host, Tree* tree);
+hipError_t enqueue_fill_adaptive(size_t n, int dim, int max_depth, size_t leaf_capacity, double theta, char* block, const TreeLayout& L,
+                                 uint32_t* list_sources, uint32_t* far_cells, hipStream_t s);
 // plan_far's blocks on the device (unit_off: the planner's padded slots): far_blocks of them, longest far list first; scratch:
 // 4 x far_blocks words + one FarBlock array of the same length
 size_t far_scratch_bytes(size_t far_blocks);

@@ -152,13 +152,17 @@ struct WalkArgs {
     uint32_t nl_max;
     int dim, depth;
     double theta;
+    const uint32_t* leaf_keys;      // the adaptive tree: a leaf's first finest key and its level
+    const uint32_t* leaf_level;
 };
 
 // The walk of one target leaf per lane, depth first from the level-1 nodes: a node the acceptance test takes goes to the far list
 // (its level's section: depth-first order within a level is Morton order), a leaf-level node it does not take goes to the near
 // list (the leaf itself in front), any other node is opened.  No frontier is stored: FILL = false counts (near, far, far per
 // level), FILL = true walks again and writes behind the offsets the counts gave.
-template <bool FILL>
+// ADAPTIVE: leaves sit at any level.  A cell that is a leaf has child_end = 0 and its leaf in child_first; the target's box is the
+// leaf's own node (accepts_box); a.depth = 0 stands for an unsplit root.
+template <bool FILL, bool ADAPTIVE>
 __global__ __launch_bounds__(kWalkLanes) void ot_walk_kernel(WalkArgs a) {
     __shared__ uint32_t cur[kMaxDepth + 1][kWalkLanes], end[kMaxDepth + 1][kWalkLanes], far_at[kMaxDepth + 1][kWalkLanes];
     const unsigned lane = threadIdx.x;
@@ -171,8 +175,9 @@ __global__ __launch_bounds__(kWalkLanes) void ot_walk_kernel(WalkArgs a) {
         if (FILL) a.list_sources[a.list_offsets[t]] = t;
     } else if (live) {
         const int depth = a.depth, dim = a.dim;
-        const uint32_t leaf_base = a.level_base[depth];
-        const uint32_t q = a.cell_coords[leaf_base + t];
+        const uint32_t leaf_base = ADAPTIVE ? 0u : a.level_base[depth];
+        const int st = ADAPTIVE ? depth - (int)a.leaf_level[t] : 0;
+        const uint32_t q = ADAPTIVE ? packed_coords(a.leaf_keys[t] >> (dim * st), dim, depth - st) : a.cell_coords[leaf_base + t];
         uint32_t near_base = 0;
         if (FILL) {
             near_base = a.list_offsets[t];
@@ -189,13 +194,14 @@ __global__ __launch_bounds__(kWalkLanes) void ot_walk_kernel(WalkArgs a) {
             const uint32_t c = cur[L][lane];
             if (c == end[L][lane]) { --L; continue; }
             cur[L][lane] = c + 1u;
-            if (accepts(q, a.cell_coords[c], dim, depth - L, a.theta)) {
+            const uint32_t stop = ADAPTIVE ? a.child_end[c] : 0u;
+            if (ADAPTIVE ? accepts_box(q, st, a.cell_coords[c], dim, depth - L, a.theta) : accepts(q, a.cell_coords[c], dim, depth - L, a.theta)) {
                 const uint32_t at = far_at[L][lane];
                 far_at[L][lane] = at + 1u;
                 if (FILL) a.far_cells[at] = c;
                 else ++far;
-            } else if (L == depth) {
-                const uint32_t leaf = c - leaf_base;
+            } else if (ADAPTIVE ? stop == 0u : L == depth) {
+                const uint32_t leaf = ADAPTIVE ? a.child_first[c] : c - leaf_base;
                 if (FILL) {
                     if (leaf == t) a.list_sources[near_base] = leaf;
                     else a.list_sources[near_base + near++] = leaf;
@@ -203,10 +209,10 @@ __global__ __launch_bounds__(kWalkLanes) void ot_walk_kernel(WalkArgs a) {
                     ++near;
                 }
             } else {
-                const uint32_t first = a.child_first[c], stop = a.child_end[c];
+                const uint32_t first = a.child_first[c];
                 ++L;
                 cur[L][lane] = first;
-                end[L][lane] = stop;
+                end[L][lane] = ADAPTIVE ? stop : a.child_end[c];
             }
         }
         if (!FILL)
@@ -233,6 +239,98 @@ __global__ __launch_bounds__(kWalkLanes) void ot_walk_kernel(WalkArgs a) {
         atomicAdd(&a.totals->far_entries, far_sum);
         atomicAdd(&a.totals->far_blocks, group_sum);
     }
+}
+
+// ---- the adaptive tree ----
+__global__ void ota_runs_done_kernel(Counts* C) { C->n_runs = C->n_leaves; }
+
+// node_start[j] = the first run of the level's j-th node (node_at: the exclusive scan of the level's run starts); one past the last: n_runs
+__global__ __launch_bounds__(256) void ota_node_starts_kernel(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ node_at, const Counts* C,
+                                                              uint32_t capacity, uint32_t* __restrict__ node_start) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t nr = C->n_runs < capacity ? C->n_runs : capacity;
+    if (r >= nr) return;
+    if (flags[r]) node_start[node_at[r]] = r;
+    if (r == 0u) node_start[node_at[nr]] = nr;
+}
+
+// a run without a leaf level yet (0) takes this level when its node here holds at most `cap` bodies
+__global__ __launch_bounds__(256) void ota_run_level_kernel(const uint32_t* __restrict__ node_at, const uint32_t* __restrict__ node_start,
+                                                            const uint32_t* __restrict__ run_off, const Counts* C, uint32_t capacity, uint32_t cap, uint32_t level,
+                                                            uint32_t* __restrict__ run_level) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t nr = C->n_runs < capacity ? C->n_runs : capacity;
+    if (r >= nr || run_level[r] != 0u) return;
+    const uint32_t j = node_at[r + 1u] - 1u;      // the starts up to and including r, less one
+    if (run_off[node_start[j + 1u]] - run_off[node_start[j]] <= cap) run_level[r] = level;
+}
+
+// a run starts a leaf when the run before it lies in another node of the run's leaf level (a node's runs share their leaf level);
+// runs still without a level take `fallback`: max_depth, or 0 under an unsplit root
+__global__ __launch_bounds__(256) void ota_leaf_flags_kernel(const uint32_t* __restrict__ run_keys, const Counts* C, uint32_t capacity, int dim, int depth,
+                                                             uint32_t fallback, uint32_t* __restrict__ run_level, uint32_t* __restrict__ flags) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t nr = C->n_runs < capacity ? C->n_runs : capacity;
+    if (r >= nr) return;
+    uint32_t lv = run_level[r];
+    if (lv == 0u) run_level[r] = lv = fallback;
+    const int shift = dim * (depth - (int)lv);
+    flags[r] = (r == 0u || (run_keys[r] >> shift) != (run_keys[r - 1u] >> shift)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void ota_leaves_kernel(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ leaf_of, const uint32_t* __restrict__ run_off,
+                                                         const uint32_t* __restrict__ run_keys, const uint32_t* __restrict__ run_level, uint32_t capacity,
+                                                         uint32_t* __restrict__ leaf_offsets, uint32_t* __restrict__ leaf_keys, uint32_t* __restrict__ leaf_level,
+                                                         Counts* C) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t nr = C->n_runs < capacity ? C->n_runs : capacity;
+    if (r >= nr) return;
+    if (r == 0u) { const uint32_t nl = leaf_of[nr]; leaf_offsets[nl] = C->n; C->n_leaves = nl; }
+    if (flags[r]) { const uint32_t l = leaf_of[r]; leaf_offsets[l] = run_off[r]; leaf_keys[l] = run_keys[r]; leaf_level[l] = run_level[r]; }
+}
+
+// flag[i] = leaf i starts an EXISTING node of `level`: it lies at that level or below, and the leaf before it under another prefix
+__global__ __launch_bounds__(256) void ota_level_flags_kernel(const uint32_t* __restrict__ leaf_keys, const uint32_t* __restrict__ leaf_level, const Counts* C,
+                                                              uint32_t capacity, uint32_t level, int shift, uint32_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t nl = C->n_leaves < capacity ? C->n_leaves : capacity;
+    if (i >= nl) return;
+    flags[i] = (leaf_level[i] >= level && (i == 0u || (leaf_keys[i] >> shift) != (leaf_keys[i - 1u] >> shift))) ? 1u : 0u;
+}
+
+// one lane per (level, leaf): the leaf that starts an existing node of the level writes the node's cell.  Its leaves end where the
+// sorted leaf keys leave the prefix (a binary search); a leaf cell keeps its leaf in child_first and 0 in child_end (a split node's
+// children end past level_base[2] >= 1); a split node's children are the next level's nodes started within its leaves.
+__global__ __launch_bounds__(256) void ota_cells_kernel(const uint32_t* __restrict__ leaf_keys, const uint32_t* __restrict__ leaf_level,
+                                                        const uint32_t* __restrict__ rank, size_t rank_stride, int dim, int depth,
+                                                        const uint32_t* __restrict__ level_base, const Counts* C, uint32_t* __restrict__ cell_first,
+                                                        uint32_t* __restrict__ cell_count, uint32_t* __restrict__ cell_coords, uint32_t* __restrict__ child_first,
+                                                        uint32_t* __restrict__ child_end, uint32_t* __restrict__ cell_key, uint32_t* __restrict__ cell_id) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t L = blockIdx.y + 1u, nl = C->n_leaves;
+    if (i >= nl || leaf_level[i] < L) return;
+    const int shift = dim * (depth - (int)L);
+    const uint32_t key = leaf_keys[i] >> shift;
+    if (i != 0u && key == (leaf_keys[i - 1u] >> shift)) return;
+    const uint32_t past = (key + 1u) << shift;      // at most 2^(dim depth) <= 2^30
+    uint32_t lo = i + 1u, hi = nl;                   // the first leaf whose key is >= past
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (leaf_keys[mid] < past) lo = mid + 1u; else hi = mid;
+    }
+    const uint32_t c = level_base[L] + rank[(size_t)L * rank_stride + i], count = lo - i;
+    cell_first[c] = i;
+    cell_count[c] = count;
+    cell_coords[c] = packed_coords(key, dim, (int)L);
+    if (leaf_level[i] == L) {
+        child_first[c] = i;
+        child_end[c] = 0u;
+    } else {
+        child_first[c] = level_base[L + 1u] + rank[(size_t)(L + 1u) * rank_stride + i];
+        child_end[c] = level_base[L + 1u] + rank[(size_t)(L + 1u) * rank_stride + i + count];
+    }
+    cell_key[c] = count > nbx_far::kSmallCell ? 1u : 0u;
+    cell_id[c] = c;
 }
 
 // leaf_far.h plan_far's blocks of one leaf per lane, in leaf order; the sort key puts the longest far list first
@@ -265,7 +363,7 @@ inline unsigned grid_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
-TreeLayout make_tree_layout(size_t n, int dim, int depth) {
+TreeLayout make_tree_layout(size_t n, int dim, int depth, bool adaptive) {
     TreeLayout L{};
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256 + 256; return o; };
@@ -307,6 +405,14 @@ TreeLayout make_tree_layout(size_t n, int dim, int depth) {
     L.cells_split = take((cells + 1) * 4);
     L.far_blk_cnt = take((nl + 1) * 4);
     L.far_blk_off = take((nl + 2) * 4);
+    if (adaptive) {
+        L.run_off = take((nl + 1) * 4);
+        L.run_keys = take((nl + 1) * 4);
+        L.run_level = take((nl + 1) * 4);
+        L.node_at = take((nl + 2) * 4);
+        L.node_start = take((nl + 2) * 4);
+        L.leaf_level = take((nl + 1) * 4);
+    }
     L.total = at;
     return L;
 }
@@ -367,7 +473,7 @@ hipError_t enqueue_build(const double* x64, size_t pad, size_t n, int dim, int d
     a.child_first = words(block, L.child_first); a.child_end = words(block, L.child_end);
     a.near_cnt = words(block, L.near_cnt); a.far_cnt = words(block, L.far_cnt); a.level_far = words(block, L.level_far); a.far_blk_cnt = words(block, L.far_blk_cnt);
     a.totals = C; a.nl_max = nl_max; a.dim = dim; a.depth = depth; a.theta = theta;
-    hipLaunchKernelGGL(ot_walk_kernel<false>, dim3((nl_max + kWalkLanes - 1u) / kWalkLanes), dim3(kWalkLanes), 0, s, a);
+    hipLaunchKernelGGL((ot_walk_kernel<false, false>), dim3((nl_max + kWalkLanes - 1u) / kWalkLanes), dim3(kWalkLanes), 0, s, a);
     OT_TRY(exclusive_scan(words(block, L.near_cnt), words(block, L.list_offsets), &C->n_leaves, nl_max, words(block, L.tile_sums), s));
     OT_TRY(exclusive_scan(words(block, L.far_cnt), words(block, L.far_offsets), &C->n_leaves, nl_max, words(block, L.tile_sums), s));
     OT_TRY(exclusive_scan(words(block, L.far_blk_cnt), words(block, L.far_blk_off), &C->n_leaves, nl_max, words(block, L.tile_sums), s));
@@ -395,7 +501,110 @@ hipError_t enqueue_fill(size_t n, int dim, int depth, double theta, char* block,
     a.list_offsets = words(block, L.list_offsets); a.far_offsets = words(block, L.far_offsets);
     a.list_sources = list_sources; a.far_cells = far_cells;
     a.totals = C; a.nl_max = (uint32_t)L.nl_max; a.dim = dim; a.depth = depth; a.theta = theta;
-    hipLaunchKernelGGL(ot_walk_kernel<true>, dim3(((unsigned)L.nl_max + kWalkLanes - 1u) / kWalkLanes), dim3(kWalkLanes), 0, s, a);
+    hipLaunchKernelGGL((ot_walk_kernel<true, false>), dim3(((unsigned)L.nl_max + kWalkLanes - 1u) / kWalkLanes), dim3(kWalkLanes), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t enqueue_build_adaptive(const double* x64, size_t pad, size_t n, int dim, int depth, size_t leaf_capacity, double theta, char* block,
+                                  const TreeLayout& L, hipStream_t s, Counts* counts_host, Tree* tree) {
+    hipError_t e;
+    const uint32_t n32 = (uint32_t)n, nl_max = (uint32_t)L.nl_max, cells_max = (uint32_t)L.cells_max;
+    const uint32_t cap = (uint32_t)std::min<size_t>(leaf_capacity, 0xffffffffu);
+    const bool split = root_is_split(n, depth, leaf_capacity);
+    Counts* const C = reinterpret_cast<Counts*>(block + L.counts);
+    RootBox* const box = reinterpret_cast<RootBox*>(block + L.box);
+    double* const partial = reinterpret_cast<double*>(block + L.partial);
+    Counts init{};
+    init.n = n32;
+    *counts_host = init;
+    OT_TRY(hipMemcpyAsync(C, counts_host, sizeof(Counts), hipMemcpyHostToDevice, s));
+    const dim3 blk(256);
+    // bounding box, root box, keys at max_depth, the stable sort: the fixed builder's stages
+    hipLaunchKernelGGL(ot_bbox_partial_kernel, dim3(kBoxBlocks), blk, 0, s, x64, pad, n32, dim, partial, C);
+    hipLaunchKernelGGL(ot_bbox_final_kernel, dim3(1), blk, 0, s, partial, kBoxBlocks, dim, box);
+    uint32_t *keys = words(block, L.key_a), *vals = words(block, L.val_a), *keys2 = words(block, L.key_b), *vals2 = words(block, L.val_b);
+    hipLaunchKernelGGL(ot_keys_kernel, dim3(grid_of(n)), blk, 0, s, x64, pad, n32, dim, depth, box, keys, vals);
+    const int passes = (dim * depth + 7) / 8;
+    for (int p = 0; p < passes; ++p) {
+        OT_TRY(radix_pass(keys, vals, keys2, vals2, &C->n, n32, 8 * p, words(block, L.hist), s));
+        std::swap(keys, keys2);
+        std::swap(vals, vals2);
+    }
+    // the finest level's runs (the fixed tree's leaves)
+    uint32_t* const flags = words(block, L.flags);
+    uint32_t *const run_off = words(block, L.run_off), *const run_keys = words(block, L.run_keys), *const run_level = words(block, L.run_level);
+    uint32_t *const node_at = words(block, L.node_at), *const node_start = words(block, L.node_start), *const leaf_level = words(block, L.leaf_level);
+    hipLaunchKernelGGL(ot_flags_kernel, dim3(grid_of(n)), blk, 0, s, keys, &C->n, n32, 0, flags);
+    OT_TRY(exclusive_scan(flags, keys2, &C->n, n32, words(block, L.tile_sums), s));
+    hipLaunchKernelGGL(ot_leaves_kernel, dim3(grid_of(n)), blk, 0, s, keys, keys2, n32, run_off, run_keys, C);
+    hipLaunchKernelGGL(ota_runs_done_kernel, dim3(1), dim3(1), 0, s, C);
+    // every run's leaf level: the first level whose node holds at most `cap` bodies (node counts from the runs' offsets), else max_depth
+    OT_TRY(hipMemsetAsync(run_level, 0, (L.nl_max + 1) * 4, s));
+    if (split)
+        for (int lv = 1; lv < depth; ++lv) {
+            hipLaunchKernelGGL(ot_flags_kernel, dim3(grid_of(nl_max)), blk, 0, s, run_keys, &C->n_runs, nl_max, dim * (depth - lv), flags);
+            OT_TRY(exclusive_scan(flags, node_at, &C->n_runs, nl_max, words(block, L.tile_sums), s));
+            hipLaunchKernelGGL(ota_node_starts_kernel, dim3(grid_of(nl_max)), blk, 0, s, flags, node_at, C, nl_max, node_start);
+            hipLaunchKernelGGL(ota_run_level_kernel, dim3(grid_of(nl_max)), blk, 0, s, node_at, node_start, run_off, C, nl_max, cap, (uint32_t)lv, run_level);
+        }
+    // the leaves: runs of equal (leaf level, prefix)
+    hipLaunchKernelGGL(ota_leaf_flags_kernel, dim3(grid_of(nl_max)), blk, 0, s, run_keys, C, nl_max, dim, depth, split ? (uint32_t)depth : 0u, run_level, flags);
+    OT_TRY(exclusive_scan(flags, node_at, &C->n_runs, nl_max, words(block, L.tile_sums), s));
+    hipLaunchKernelGGL(ota_leaves_kernel, dim3(grid_of(nl_max)), blk, 0, s, flags, node_at, run_off, run_keys, run_level, nl_max, words(block, L.leaf_offsets),
+                       words(block, L.leaf_keys), leaf_level, C);
+    // the existing nodes of every level
+    const size_t rank_stride = L.nl_max + 1;
+    uint32_t* const rank = words(block, L.rank);
+    for (int lv = 1; lv <= depth; ++lv) {
+        hipLaunchKernelGGL(ota_level_flags_kernel, dim3(grid_of(nl_max)), blk, 0, s, words(block, L.leaf_keys), leaf_level, C, nl_max, (uint32_t)lv,
+                           dim * (depth - lv), flags);
+        OT_TRY(exclusive_scan(flags, rank + (size_t)lv * rank_stride, &C->n_leaves, nl_max, words(block, L.tile_sums), s));
+    }
+    hipLaunchKernelGGL(ot_level_bases_kernel, dim3(1), dim3(1), 0, s, rank, rank_stride, depth, words(block, L.level_base), C);
+    if (split) {
+        hipLaunchKernelGGL(ota_cells_kernel, dim3(grid_of(nl_max), (unsigned)depth), blk, 0, s, words(block, L.leaf_keys), leaf_level, rank, rank_stride, dim, depth,
+                           words(block, L.level_base), C, words(block, L.cell_first), words(block, L.cell_count), words(block, L.cell_coords),
+                           words(block, L.child_first), words(block, L.child_end), words(block, L.cell_key), words(block, L.cell_id));
+        OT_TRY(radix_pass(words(block, L.cell_key), words(block, L.cell_id), words(block, L.cell_key2), words(block, L.cells_split), &C->n_cells, cells_max, 0,
+                          words(block, L.hist), s));
+        hipLaunchKernelGGL(ot_small_count_kernel, dim3(1), dim3(1), 0, s, words(block, L.hist), sort_tiles(cells_max), C);
+    }
+    // the counting walk and the offsets of both lists
+    WalkArgs a{};
+    a.C = C; a.level_base = words(block, L.level_base); a.leaf_offsets = words(block, L.leaf_offsets); a.cell_coords = words(block, L.cell_coords);
+    a.child_first = words(block, L.child_first); a.child_end = words(block, L.child_end);
+    a.near_cnt = words(block, L.near_cnt); a.far_cnt = words(block, L.far_cnt); a.level_far = words(block, L.level_far); a.far_blk_cnt = words(block, L.far_blk_cnt);
+    a.totals = C; a.nl_max = nl_max; a.dim = dim; a.depth = split ? depth : 0; a.theta = theta;
+    a.leaf_keys = words(block, L.leaf_keys); a.leaf_level = leaf_level;
+    hipLaunchKernelGGL((ot_walk_kernel<false, true>), dim3((nl_max + kWalkLanes - 1u) / kWalkLanes), dim3(kWalkLanes), 0, s, a);
+    OT_TRY(exclusive_scan(words(block, L.near_cnt), words(block, L.list_offsets), &C->n_leaves, nl_max, words(block, L.tile_sums), s));
+    OT_TRY(exclusive_scan(words(block, L.far_cnt), words(block, L.far_offsets), &C->n_leaves, nl_max, words(block, L.tile_sums), s));
+    OT_TRY(exclusive_scan(words(block, L.far_blk_cnt), words(block, L.far_blk_off), &C->n_leaves, nl_max, words(block, L.tile_sums), s));
+    OT_TRY(hipGetLastError());
+    OT_TRY(hipMemcpyAsync(counts_host, C, sizeof(Counts), hipMemcpyDeviceToHost, s));
+    tree->counts = C;
+    tree->leaf_offsets = words(block, L.leaf_offsets);
+    tree->leaf_bodies = vals;
+    tree->list_offsets = words(block, L.list_offsets);
+    tree->far_offsets = words(block, L.far_offsets);
+    tree->cell_first = words(block, L.cell_first);
+    tree->cell_count = words(block, L.cell_count);
+    tree->small_cells = words(block, L.cells_split);
+    return hipSuccess;
+}
+
+hipError_t enqueue_fill_adaptive(size_t n, int dim, int depth, size_t leaf_capacity, double theta, char* block, const TreeLayout& L, uint32_t* list_sources,
+                                 uint32_t* far_cells, hipStream_t s) {
+    Counts* const C = reinterpret_cast<Counts*>(block + L.counts);
+    WalkArgs a{};
+    a.C = C; a.level_base = words(block, L.level_base); a.leaf_offsets = words(block, L.leaf_offsets); a.cell_coords = words(block, L.cell_coords);
+    a.child_first = words(block, L.child_first); a.child_end = words(block, L.child_end);
+    a.level_far = words(block, L.level_far);
+    a.list_offsets = words(block, L.list_offsets); a.far_offsets = words(block, L.far_offsets);
+    a.list_sources = list_sources; a.far_cells = far_cells;
+    a.totals = C; a.nl_max = (uint32_t)L.nl_max; a.dim = dim; a.depth = root_is_split(n, depth, leaf_capacity) ? depth : 0; a.theta = theta;
+    a.leaf_keys = words(block, L.leaf_keys); a.leaf_level = words(block, L.leaf_level);
+    hipLaunchKernelGGL((ot_walk_kernel<true, true>), dim3(((unsigned)L.nl_max + kWalkLanes - 1u) / kWalkLanes), dim3(kWalkLanes), 0, s, a);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include <unordered_map>
 
 #include "nbody_hip.h"
+#include "../csrc/octree_device.h"   // its plain C++ part: root_box, body_key, packed_coords, accepts_box (one definition, host and device)
 
 namespace {
 thread_local float g_leaf_ms = 0.0f;
@@ -137,11 +138,13 @@ template <int D>
 struct OctreeOnDevice {
     nbx_ctx* ctx = nullptr;
     nbx_leaf_plan* plan = nullptr;
-    OctreeOnDevice(const std::vector<Body<D>>& bodies, double theta, int depth, const char* where) {
+    // leaf_capacity < 0: the fixed-depth tree (depth 0: barnes_hut_hip_depth); otherwise the adaptive one, depth = max_depth
+    OctreeOnDevice(const std::vector<Body<D>>& bodies, double theta, int depth, const char* where, int leaf_capacity = -1) {
         const int device = leaf_device();
         int rc = nbx_ctx_create(&ctx, device, D, bodies.size(), 1, 0);
         if (!rc) rc = nbx_ctx_upload_bodies(ctx, bodies.data(), sizeof(Body<D>));
-        if (!rc) rc = nbx_leaf_plan_create_octree(&plan, ctx, depth > 0 ? depth : barnes_hut_hip_depth(bodies.size(), D), theta);
+        if (!rc && leaf_capacity >= 0) rc = nbx_leaf_plan_create_octree_adaptive(&plan, ctx, depth, leaf_capacity, theta);
+        else if (!rc) rc = nbx_leaf_plan_create_octree(&plan, ctx, depth > 0 ? depth : barnes_hut_hip_depth(bodies.size(), D), theta);
         if (rc != NBX_OK) {
             nbx_leaf_plan_destroy(plan);
             nbx_ctx_destroy(ctx);
@@ -174,6 +177,52 @@ void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth,
     if (rc != NBX_OK) raise_leaf("barnes_hut_hip_steps", rc);
 }
 
+namespace {
+void check_capacity(int leaf_capacity, const char* where) {
+    if (leaf_capacity < 0) throw std::runtime_error(std::string(where) + ": leaf_capacity must be >= 0");
+}
+}  // namespace
+
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth) {
+    check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_n_body");
+    std::vector<Vector<D>> forces(bodies.size());
+    if (bodies.empty()) return forces;
+    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_n_body", leaf_capacity);
+    const int rc = nbx_leaf_plan_forces_ctx(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, reinterpret_cast<double*>(forces.data()), nullptr);
+    if (rc != NBX_OK) raise_leaf("barnes_hut_hip_adaptive_n_body", rc);
+    return forces;
+}
+
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every) {
+    check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_steps");
+    if (bodies.empty()) return;
+    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_steps", leaf_capacity);
+    int rc = nbx_leaf_plan_step_octree(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, dt, nsteps, rebuild_every);
+    if (!rc) rc = nbx_ctx_download_bodies(tree.ctx, bodies.data(), sizeof(Body<D>));
+    if (rc != NBX_OK) raise_leaf("barnes_hut_hip_adaptive_steps", rc);
+}
+
+template <int D>
+void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, std::size_t* n_leaves, std::size_t* largest_leaf) {
+    check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_leaves");
+    *n_leaves = *largest_leaf = 0;
+    if (bodies.empty()) return;
+    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_leaves", leaf_capacity);
+    int rc = nbx_leaf_plan_structure_sizes(tree.plan, n_leaves, nullptr, nullptr, nullptr);
+    std::vector<std::uint32_t> offsets(*n_leaves + 1);
+    if (!rc) rc = nbx_leaf_plan_get_structure(tree.plan, offsets.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != NBX_OK) raise_leaf("barnes_hut_hip_adaptive_leaves", rc);
+    for (std::size_t l = 0; l < *n_leaves; ++l) *largest_leaf = std::max<std::size_t>(*largest_leaf, offsets[l + 1] - offsets[l]);
+}
+
+template std::vector<Vector<2>> barnes_hut_hip_adaptive_n_body<2>(const std::vector<Body<2>>&, double, int, int);
+template std::vector<Vector<3>> barnes_hut_hip_adaptive_n_body<3>(const std::vector<Body<3>>&, double, int, int);
+template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int);
+template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int);
+template void barnes_hut_hip_adaptive_leaves<2>(const std::vector<Body<2>>&, double, int, int, std::size_t*, std::size_t*);
+template void barnes_hut_hip_adaptive_leaves<3>(const std::vector<Body<3>>&, double, int, int, std::size_t*, std::size_t*);
 template std::vector<Vector<2>> barnes_hut_hip_n_body<2>(const std::vector<Body<2>>&, double, int);
 template std::vector<Vector<3>> barnes_hut_hip_n_body<3>(const std::vector<Body<3>>&, double, int);
 template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int);
@@ -322,6 +371,121 @@ LeafLists build_octree_cells(const std::vector<Body<D>>& bodies, int depth, doub
     return L;
 }
 
+// The cell index, the keys and the acceptance test must round as numpy's two-step arithmetic does: no fused multiply-adds from here on.
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#pragma GCC optimize("fp-contract=off")
+#endif
+
+template <int D>
+LeafLists build_adaptive_octree_cells(const std::vector<Body<D>>& bodies, int max_depth, int leaf_capacity, double theta) {
+    namespace ot = nbx_octree;
+    if (max_depth < 0 || max_depth > ot::kMaxDepth || leaf_capacity < 0 || !(theta >= 0.0) || !std::isfinite(theta))
+        throw std::invalid_argument("build_adaptive_octree_cells: max_depth in [0, 10], leaf_capacity >= 0, theta finite and >= 0");
+    LeafLists L;
+    L.far_offsets.assign(1, 0u);
+    const std::size_t n = bodies.size(), cap = (std::size_t)leaf_capacity;
+    if (n == 0) return L;
+    const int depth = max_depth;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    for (int d = 0; d < D; ++d) lo[d] = hi[d] = bodies[0].position[d];
+    for (const auto& b : bodies)
+        for (int d = 0; d < D; ++d) { lo[d] = std::min(lo[d], b.position[d]); hi[d] = std::max(hi[d], b.position[d]); }
+    const ot::RootBox box = ot::root_box(lo, hi, D);
+    std::vector<std::uint32_t> key(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        double x[3] = {0, 0, 0};
+        for (int d = 0; d < D; ++d) x[d] = bodies[i].position[d];
+        key[i] = ot::body_key(x, box, D, depth);
+    }
+    std::vector<std::uint32_t> order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](std::uint32_t a, std::uint32_t b) { return key[a] < key[b]; });
+    L.leaf_bodies = order;
+    if (!ot::root_is_split(n, depth, cap)) {                       // one leaf, its near list itself, no cells
+        L.leaf_offsets = {0u, (std::uint32_t)n};
+        L.list_offsets = {0u, 1u};
+        L.list_sources = {0u};
+        L.far_offsets = {0u, 0u};
+        return L;
+    }
+    // the finest level's runs, and every run's leaf level: the first level whose node holds at most `cap` bodies, else max_depth
+    std::vector<std::uint32_t> run_key, run_off;
+    for (std::size_t s = 0; s < n; ++s)
+        if (s == 0 || key[order[s]] != key[order[s - 1]]) { run_key.push_back(key[order[s]]); run_off.push_back((std::uint32_t)s); }
+    run_off.push_back((std::uint32_t)n);
+    const std::size_t nr = run_key.size();
+    std::vector<int> run_level(nr, 0);
+    for (int lv = 1; lv <= depth; ++lv) {
+        const int shift = D * (depth - lv);
+        for (std::size_t r = 0; r < nr;) {
+            std::size_t e = r + 1;
+            while (e < nr && (run_key[e] >> shift) == (run_key[r] >> shift)) ++e;
+            const bool leaf = lv == depth || (cap > 0 && run_off[e] - run_off[r] <= cap);
+            for (std::size_t i = r; i < e; ++i)
+                if (run_level[i] == 0 && leaf) run_level[i] = lv;
+            r = e;
+        }
+    }
+    std::vector<std::uint32_t> leaf_key;
+    std::vector<int> leaf_level;
+    L.leaf_offsets.clear();
+    for (std::size_t r = 0; r < nr; ++r) {
+        const int shift = D * (depth - run_level[r]);
+        if (r == 0 || (run_key[r] >> shift) != (run_key[r - 1] >> shift)) { leaf_key.push_back(run_key[r]); leaf_level.push_back(run_level[r]); L.leaf_offsets.push_back(run_off[r]); }
+    }
+    L.leaf_offsets.push_back((std::uint32_t)n);
+    const std::size_t nl = leaf_key.size();
+    // the existing nodes of levels 1 .. depth: prefix, first leaf, leaf count, leaf or split, the id of the level's first cell
+    struct Level { std::vector<std::uint32_t> key, first, count; std::vector<char> leaf; std::size_t base = 0; };
+    std::vector<Level> lv_of(depth + 2);
+    for (int lv = 1; lv <= depth; ++lv) {
+        Level& V = lv_of[lv];
+        V.base = L.cell_first_leaf.size();
+        const int shift = D * (depth - lv);
+        for (std::size_t l = 0; l < nl; ++l) {
+            if (leaf_level[l] < lv) continue;
+            const std::uint32_t k = leaf_key[l] >> shift;
+            if (V.key.empty() || V.key.back() != k) { V.key.push_back(k); V.first.push_back((std::uint32_t)l); V.count.push_back(0u); V.leaf.push_back(leaf_level[l] == lv); }
+            ++V.count.back();
+        }
+        L.cell_first_leaf.insert(L.cell_first_leaf.end(), V.first.begin(), V.first.end());
+        L.cell_leaf_count.insert(L.cell_leaf_count.end(), V.count.begin(), V.count.end());
+    }
+    L.list_offsets.assign(1, 0u);
+    std::vector<std::size_t> frontier, next;
+    std::vector<std::uint32_t> others;
+    for (std::size_t t = 0; t < nl; ++t) {
+        const int st = depth - leaf_level[t];
+        const std::uint32_t q = ot::packed_coords(leaf_key[t] >> (D * st), D, leaf_level[t]);
+        frontier.resize(lv_of[1].key.size());
+        std::iota(frontier.begin(), frontier.end(), (std::size_t)0);
+        others.clear();
+        for (int lv = 1; lv <= depth && !frontier.empty(); ++lv) {
+            const Level& V = lv_of[lv];
+            next.clear();
+            for (const std::size_t node : frontier) {
+                if (ot::accepts_box(q, st, ot::packed_coords(V.key[node], D, lv), D, depth - lv, theta)) { L.far_cells.push_back((std::uint32_t)(V.base + node)); continue; }
+                if (V.leaf[node]) { if (V.first[node] != t) others.push_back(V.first[node]); continue; }
+                const auto& kids = lv_of[lv + 1].key;
+                const std::size_t k0 = (std::size_t)(std::lower_bound(kids.begin(), kids.end(), V.key[node] << D) - kids.begin());
+                const std::size_t k1 = (std::size_t)(std::lower_bound(kids.begin(), kids.end(), (V.key[node] + 1u) << D) - kids.begin());
+                for (std::size_t k = k0; k < k1; ++k) next.push_back(k);
+            }
+            frontier.swap(next);
+        }
+        std::sort(others.begin(), others.end());
+        L.list_sources.push_back((std::uint32_t)t);                       // the leaf itself first, the others in leaf order
+        L.list_sources.insert(L.list_sources.end(), others.begin(), others.end());
+        L.list_offsets.push_back((std::uint32_t)L.list_sources.size());
+        L.far_offsets.push_back((std::uint32_t)L.far_cells.size());
+    }
+    return L;
+}
+
+template LeafLists build_adaptive_octree_cells<2>(const std::vector<Body<2>>&, int, int, double);
+template LeafLists build_adaptive_octree_cells<3>(const std::vector<Body<3>>&, int, int, double);
 template LeafLists build_octree_cells<2>(const std::vector<Body<2>>&, int, double);
 template LeafLists build_octree_cells<3>(const std::vector<Body<3>>&, int, double);
 template std::vector<Vector<2>> leaf_pair_direct_forces_hip<2>(const std::vector<Body<2>>&, const LeafLists&, LeafLaw);

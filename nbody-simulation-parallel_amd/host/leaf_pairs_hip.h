@@ -78,6 +78,16 @@ LeafLists build_uniform_leaves(const std::vector<Body<D>>& bodies, int depth);
 template <int D>
 LeafLists build_octree_cells(const std::vector<Body<D>>& bodies, int depth, double theta);
 
+// An ADAPTIVE octree with near and far lists, the twin of nbody_amd.leaves.adaptive_octree_cells and the specification of
+// nbx_leaf_plan_create_octree_adaptive: root box, finest cells, Morton keys and body order of build_octree_cells(depth = max_depth);
+// the root is split when max_depth >= 1 and (leaf_capacity == 0 or n > leaf_capacity); a node exists when it is not empty and its
+// parent is split; an existing node is a leaf at max_depth or, for leaf_capacity > 0, with at most leaf_capacity bodies.  Leaves in
+// Morton order, cells = the existing nodes of levels 1 .. max_depth level by level, and a walk per target leaf with the leaf's own
+// box (octree_device.h accepts_box).  leaf_capacity = 0 gives build_octree_cells's arrays.  Throws std::invalid_argument for
+// max_depth outside [0, 10], a negative capacity or a theta that is negative or not finite.
+template <int D>
+LeafLists build_adaptive_octree_cells(const std::vector<Body<D>>& bodies, int max_depth, int leaf_capacity, double theta);
+
 // Barnes-Hut with the tree built ON THE DEVICE, in the shape of the reference's barnes_hut_seq_n_body (methods.h:47): bodies in,
 // forces out, a new tree per call (methods.cpp:377-401).  The bodies go to a context, the fixed-depth octree, its near and far
 // lists and the plan's layout are made there (nbx_leaf_plan_create_octree), one evaluation under the tree-leaf law with the
@@ -90,6 +100,16 @@ int barnes_hut_hip_depth(std::size_t n_bodies, int dim);
 // (nbx_leaf_plan_step_octree), the bodies brought back at the end.
 template <int D>
 void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every = 1);
+
+// The same two calls over the ADAPTIVE octree (nbx_leaf_plan_create_octree_adaptive): leaves of at most leaf_capacity bodies down to
+// max_depth.  The tree for inputs whose density varies -- a Plummer sphere's centre -- where a fixed depth leaves cells of thousands.
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth = 10);
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every = 1);
+// leaves and largest leaf of the adaptive tree the device builds from `bodies` (what nbody_sim --leaf-cap reports)
+template <int D>
+void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, std::size_t* n_leaves, std::size_t* largest_leaf);
 
 // kernel time of the most recent leaf_pair_direct_forces_hip call on this thread (ms)
 float last_leaf_pair_kernel_ms();

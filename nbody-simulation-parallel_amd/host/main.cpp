@@ -52,6 +52,7 @@ struct Options {
     std::vector<int> devices;       // --gpus / --devices: shard the HIP rows over these GPUs (one process)
     double theta = 0.5;             // --theta: opening angle of the `-m t` row (methods.h:47's default)
     int depth = 0;                  // --depth: octree depth of the `-m t` row (0: at most 16 bodies per cell on average)
+    int leaf_cap = 0;               // --leaf-cap k > 0: `-m t` builds the adaptive octree (leaves of <= k bodies; --depth = max depth, default 10)
     double refine = -1.0;           // --refine tol: per-body relative tolerance of the HIP rows (mixed mode); 0 = plain fp32; < 0: library default (1e-5)
 };
 
@@ -269,7 +270,45 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
 
     // Barnes-Hut with the octree built on the device: `-m t`.  The whole call is timed, as the reference times barnes_hut_seq_n_body
     // (a new tree per call, methods.cpp:377-401): upload, tree, lists, layout, moments, near and far pass, forces back.
-    if (m.find('t') != std::string::npos) {
+    if (m.find('t') != std::string::npos && opt.leaf_cap > 0) {
+        // the adaptive tree: leaves of at most --leaf-cap bodies down to --depth levels
+        const int max_depth = opt.depth > 0 ? opt.depth : 10;
+        out << "Barnes-Hut on HIP (adaptive octree, at most " << opt.leaf_cap << " bodies per leaf down to depth " << max_depth << ", built on the device, theta "
+            << opt.theta << "):" << std::endl;
+        Forces forces;
+        const long long us = safely_execute(log, "BarnesHut_HIP_adaptive", [&] { forces = barnes_hut_hip_adaptive_n_body<D>(bodies, opt.theta, opt.leaf_cap, max_depth); return 0; });
+        if (us >= 0) {
+            const double seconds = static_cast<double>(us) / 1e6;
+            csv << "BarnesHut_HIP_adaptive," << n << "," << D;
+            write_time(csv, seconds);
+            if (opt.accuracy) csv << "," << std::fixed << std::setprecision(2) << compute_accuracy<D>(forces, reference);
+            csv << std::endl;
+            out << "Time taken: " << seconds << " s" << std::endl;
+            std::size_t n_leaves = 0, largest = 0;
+            if (safely_execute(log, "BarnesHut_HIP_adaptive_leaves", [&] { barnes_hut_hip_adaptive_leaves<D>(bodies, opt.theta, opt.leaf_cap, max_depth, &n_leaves, &largest); return 0; }) >= 0)
+                out << "Leaves: " << n_leaves << ", largest leaf: " << largest << " bodies" << std::endl;
+            if (opt.accuracy) out << "Accuracy: " << std::to_string(compute_accuracy<D>(forces, reference)) << "%" << std::endl;
+            print_validation_forces<D>(forces, n, log);
+            print_validation_forces<D>(forces, n, std::cout);
+            if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive.f64", forces);
+            if (opt.steps > 0) {
+                std::vector<Body<D>> state = bodies;
+                const long long step_us = safely_execute(log, "BarnesHut_HIP_adaptive_steps", [&] {
+                    barnes_hut_hip_adaptive_steps<D>(state, opt.theta, opt.leaf_cap, max_depth, opt.dt, opt.steps, 1);
+                    return 0;
+                });
+                if (step_us >= 0) {
+                    csv << "BarnesHut_HIP_adaptive_steps," << n << "," << D;
+                    write_time(csv, static_cast<double>(step_us) / 1e6);
+                    csv << std::endl;
+                    out << "Barnes-Hut on HIP (adaptive), " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
+                        << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
+                    if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive_steps.f64", state);
+                }
+            }
+        }
+        out << std::endl;
+    } else if (m.find('t') != std::string::npos) {
         const int depth = opt.depth > 0 ? opt.depth : barnes_hut_hip_depth(static_cast<std::size_t>(n), D);
         out << "Barnes-Hut on HIP (octree of depth " << depth << " built on the device, theta " << opt.theta << "):" << std::endl;
         Forces forces;
@@ -464,6 +503,7 @@ void usage(const char* argv0) {
               << "      --law <reference|newton> Pair law of the stepping loop: the reference's r^-4 form (default) or the attractive" << std::endl
               << "                      softened Newtonian law (extension; needs --softening; Plummer velocities then use --G)" << std::endl
               << "      --softening <eps> Plummer softening of the stepping loop's pair law (extension; default 0 = the reference's law)" << std::endl
+              << "      --leaf-cap <k>  -m t builds the ADAPTIVE octree: leaves of at most k bodies, --depth the deepest level (default 10); 0: fixed depth" << std::endl
               << "      --energy-every <k> Log total energy and |dE/E0| every k steps (potential matching the selected law)" << std::endl
               << "      --refine <tol>  Per-body relative tolerance of the HIP rows: fp32 for all bodies + fp64 re-evaluation of those whose" << std::endl
               << "                      fp32 sum cannot be trusted to <tol> (default 1e-5: every body within 1e-5 of the sequential reference);" << std::endl
@@ -519,6 +559,8 @@ int main(int argc, char* argv[]) {
             opt.theta = std::stod(argv[++i]);
         } else if (arg == "--depth" && has_value) {
             opt.depth = std::stoi(argv[++i]);
+        } else if (arg == "--leaf-cap" && has_value) {
+            opt.leaf_cap = std::stoi(argv[++i]);
         } else if (arg == "--G" && has_value) {
             opt.G = std::stod(argv[++i]);
         } else if (arg == "--energy-every" && has_value) {

@@ -241,3 +241,112 @@ def octree_cells(bodies: np.ndarray, dim: int, depth: int, theta: float, chunk_l
     else:
         cell_first = cell_count = none
     return (u32(leaf_offsets), u32(order), u32(list_offsets), u32(near_s), u32(cell_first), u32(cell_count), u32(far_offsets), u32(far_c))
+
+
+def adaptive_octree_cells(bodies: np.ndarray, dim: int, max_depth: int, leaf_capacity: int, theta: float, chunk_leaves: int = 16384):
+    """An ADAPTIVE octree (quadtree in 2D) with near and far lists: the eight uint32 arrays of octree_cells, for
+    nbx_leaf_plan_set_cells, and the specification of nbx_leaf_plan_create_octree_adaptive.  Root box, cells at `max_depth`, Morton
+    keys and the stable body order are those of octree_cells(depth = max_depth).  A node is a key prefix at level L <= max_depth; the
+    root is split when max_depth >= 1 and (leaf_capacity == 0 or n > leaf_capacity); a node of level L >= 1 exists when it is not
+    empty and its parent is split; an existing node is a LEAF at L == max_depth or, for leaf_capacity > 0, when it holds at most
+    leaf_capacity bodies, and is split otherwise.  Leaves are numbered in Morton order (every node is a contiguous leaf range); cells
+    are the existing nodes of levels 1 .. max_depth, level by level, Morton order within a level -- every leaf is one of them.
+    The walk of target leaf t uses the leaf's OWN node box: in units of the finest grid gap_d = max(0, node_lo - (t_lo + t_side),
+    t_lo - (node_lo + node_side)), and a node is accepted (far list: coarse levels first, Morton order within a level) when
+    float(node_side) < theta * sqrt(sum gap_d^2); a node that is not accepted goes to the near list when it is a leaf (t first, the
+    others in leaf order) and is opened otherwise.  leaf_capacity = 0 gives octree_cells(depth = max_depth) word for word; an unsplit
+    root gives one leaf, its near list itself, and no cells."""
+    if not 0 <= int(max_depth) <= 10 or int(leaf_capacity) < 0 or not (theta >= 0.0 and np.isfinite(theta)):
+        raise ValueError("max_depth in [0, 10], leaf_capacity >= 0, theta finite and >= 0")
+    pos = np.asarray(bodies)[:, :dim]
+    n, depth, cap = pos.shape[0], int(max_depth), int(leaf_capacity)
+    u32 = lambda a: np.asarray(a, dtype=np.uint32)
+    none = np.zeros(0, dtype=np.uint32)
+    if n == 0:
+        z = np.zeros(1, dtype=np.uint32)
+        return z, none, z.copy(), none.copy(), none.copy(), none.copy(), z.copy(), none.copy()
+    g = 1 << depth
+    lo, hi = pos.min(axis=0), pos.max(axis=0)                      # root box and cells: octree_cells's expressions
+    centre, half = (lo + hi) / 2.0, max(float((hi - lo).max()) / 2.0 * 1.01, 1e-300)
+    cell = np.clip(np.floor((pos - (centre - half)) / (2.0 * half) * g).astype(np.int64), 0, g - 1)
+    key = _morton_keys(cell, dim, depth)
+    order = np.argsort(key, kind="stable")
+    if not (depth >= 1 and (cap == 0 or n > cap)):                 # the root is not split
+        return u32([0, n]), u32(order), u32([0, 1]), u32([0]), none, none.copy(), u32([0, 0]), none.copy()
+    keys, first = np.unique(key[order], return_index=True)         # the finest level's runs
+    nr = keys.size
+    run_off = np.append(first, n)
+    # every run's leaf level: the first level whose node holds at most `cap` bodies, else max_depth
+    run_level = np.full(nr, depth, dtype=np.int64)
+    if cap > 0:
+        for L in range(depth - 1, 0, -1):                          # coarser levels overwrite finer ones: the first such level stays
+            _, f, inv = np.unique(keys >> (dim * (depth - L)), return_index=True, return_inverse=True)
+            count = run_off[np.append(f[1:], nr)] - run_off[f]
+            small = count[inv] <= cap
+            run_level[small] = L
+    shift = dim * (depth - run_level)
+    start = np.ones(nr, dtype=bool)
+    start[1:] = (keys[1:] >> shift[1:]) != (keys[:-1] >> shift[1:])
+    lead = np.nonzero(start)[0]
+    nl = lead.size
+    leaf_offsets, leaf_key, leaf_level = np.append(run_off[lead], n), keys[lead], run_level[lead]
+    # the existing nodes of every level: keys (sorted), leaf ranges, coordinates, leaf or split, children (a range of the next level)
+    lv_keys, lv_first, lv_count, lv_coords, lv_base, lv_leaf = {}, {}, {}, {}, {}, {}
+    leaf_cell = np.zeros(nl, dtype=np.int64)                       # a leaf's own node within its level
+    base = 0
+    for L in range(1, depth + 1):
+        s = dim * (depth - L)
+        under = np.nonzero(leaf_level >= L)[0]
+        kl, f = np.unique(leaf_key[under] >> s, return_index=True)
+        fl = under[f]
+        lv_keys[L], lv_first[L], lv_coords[L], lv_base[L] = kl, fl, _morton_coords(kl, dim, L), base
+        lv_count[L] = np.searchsorted(leaf_key, (kl + 1) << s) - fl
+        lv_leaf[L] = leaf_level[fl] == L
+        leaf_cell[fl[lv_leaf[L]]] = np.nonzero(lv_leaf[L])[0]
+        base += kl.size
+    child_first, child_count = {}, {}
+    for L in range(1, depth):
+        child_first[L] = np.searchsorted(lv_keys[L + 1], lv_keys[L] << dim)
+        child_count[L] = np.searchsorted(lv_keys[L + 1], (lv_keys[L] + 1) << dim) - child_first[L]
+    t_side = np.int64(1) << (depth - leaf_level)                   # the target boxes, in units of the finest grid
+    t_lo = np.zeros((nl, dim), dtype=np.int64)
+    for L in range(1, depth + 1):
+        at = np.nonzero(leaf_level == L)[0]
+        t_lo[at] = lv_coords[L][leaf_cell[at]] << (depth - L)
+    near_t, near_s, far_t, far_c = [], [], [], []
+    for t0 in range(0, nl, max(1, int(chunk_leaves))):
+        t1 = min(nl, t0 + max(1, int(chunk_leaves)))
+        n1 = lv_keys[1].size
+        t = np.repeat(np.arange(t0, t1, dtype=np.int64), n1)
+        node = np.tile(np.arange(n1, dtype=np.int64), t1 - t0)
+        ft, fc, nt, ns = [], [], [], []
+        for L in range(1, depth + 1):
+            s = depth - L
+            blo = lv_coords[L][node] << s
+            qlo, qs = t_lo[t], t_side[t][:, None]
+            gap = np.maximum(0, np.maximum(blo - (qlo + qs), qlo - (blo + (1 << s))))
+            acc = float(1 << s) < theta * np.sqrt((gap * gap).sum(axis=1).astype(np.float64))
+            ft.append(t[acc]); fc.append(lv_base[L] + node[acc])
+            t, node = t[~acc], node[~acc]
+            is_leaf = lv_leaf[L][node]
+            nt.append(t[is_leaf]); ns.append(lv_first[L][node[is_leaf]])
+            t, node = t[~is_leaf], node[~is_leaf]
+            if L == depth or t.size == 0:
+                break
+            cnt = child_count[L][node]
+            begin = np.repeat(np.cumsum(cnt) - cnt, cnt)
+            kid = np.repeat(child_first[L][node], cnt) + (np.arange(int(cnt.sum()), dtype=np.int64) - begin)
+            t, node = np.repeat(t, cnt), kid
+        nt, ns = np.concatenate(nt), np.concatenate(ns)
+        by = np.lexsort((ns, ns != nt, nt))                        # per leaf: itself first, then the others in leaf order
+        near_t.append(nt[by]); near_s.append(ns[by])
+        ft, fc = np.concatenate(ft), np.concatenate(fc)
+        by = np.argsort(ft, kind="stable")                         # per leaf: coarse levels first, Morton order within a level
+        far_t.append(ft[by]); far_c.append(fc[by])
+    near_t, near_s = np.concatenate(near_t), np.concatenate(near_s)
+    far_t, far_c = np.concatenate(far_t), np.concatenate(far_c)
+    list_offsets = np.concatenate([[0], np.cumsum(np.bincount(near_t, minlength=nl))])
+    far_offsets = np.concatenate([[0], np.cumsum(np.bincount(far_t, minlength=nl))])
+    cell_first = np.concatenate([lv_first[L] for L in range(1, depth + 1)])
+    cell_count = np.concatenate([lv_count[L] for L in range(1, depth + 1)])
+    return (u32(leaf_offsets), u32(order), u32(list_offsets), u32(near_s), u32(cell_first), u32(cell_count), u32(far_offsets), u32(far_c))
