@@ -11,6 +11,7 @@ import subprocess
 
 import numpy as np
 
+import sym_probe
 from oracle_lib import TOL_BACKWARD
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,10 +27,12 @@ def _build(tmp_path, src, extra=()):
 
 def test_every_pair_is_met_once_and_every_plane_entry_has_one_writer(tmp_path):
     """B even and odd, ragged last super-block, shards below one and below two super-blocks, the benchmark's 2^20, the largest
-    shard with a plan and the first without."""
+    shard with a plan and the first without; and the shapes above 2^20 bodies that tests/test_gpu_sym_large.py runs (more than
+    one visitor chunk per slice, S down to 1, 128 slots), line by line against the table of tests/sym_probe.py."""
     exe = _build(tmp_path, "sym_plan_check.cpp", ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
     pads = [0, 4096, 8192, 12288, 16384, 20480, 24576, 28672, 32768, 65536, 69632, 131072, 1 << 20, (1 << 20) + 4096,
             191 * 8192, 254 * 8192 + 4096, 255 * 8192, 1 << 21, 1 << 22]
+    pads += [pad for pad in sym_probe.TABLE if pad not in pads]
     p = subprocess.run([exe, *map(str, pads)], capture_output=True, text=True)
     assert p.returncode == 0 and f"OK {len(pads)} shard sizes" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
     lines = {int(l.split(":")[0][4:]): l for l in p.stdout.splitlines() if l.startswith("pad=")}
@@ -37,6 +40,47 @@ def test_every_pair_is_met_once_and_every_plane_entry_has_one_writer(tmp_path):
         assert "no plan" in lines[pad], lines[pad]
     assert "B=128 S=32 K=64 G=4 workgroups=4096 slots=96" in lines[1 << 20], lines[1 << 20]   # the shape DESIGN.md section 3 states
     assert "B=3 " in lines[20480] and "B=9 " in lines[69632]                                    # odd, ragged
+    assert len(sym_probe.TABLE) == 8 and set(sym_probe.TABLE) <= set(lines)
+    for pad, row in sym_probe.TABLE.items():
+        if row is None:
+            assert "no plan" in lines[pad] and sym_probe.plan(pad) is None, lines[pad]
+            continue
+        B, S, K, G, chunks, workgroups, slots = row
+        assert f"B={B} S={S} K={K} G={G} workgroups={workgroups} slots={slots} ok" in lines[pad], lines[pad]
+        assert chunks == G // min(G, 4) and chunks > 1 and workgroups == B * S and slots == S + K <= 128
+    # the Python restatement of the rule that the GPU tests state their expectations with, against the header on every size
+    for pad, line in lines.items():
+        q = sym_probe.plan(pad)
+        if q is None:
+            assert "no plan" in line, line
+        else:
+            assert "B={B} S={S} K={K} G={G} workgroups={workgroups} slots={slots} ok".format(**q) in line, (q, line)
+
+
+def test_sparse_mass_probe_covers_the_decomposition_and_its_reference_is_sound(oracle):
+    """The inputs of tests/test_gpu_sym_large.py's probe, on the host: at every shard size the heavy bodies reach every
+    chunk position the pass walks (first, later and last chunk of a slice), both ends of its rotation (super-blocks 0, 1,
+    K, K + 1, B - 1 and the antipodal partners), the last valid body and two bodies of one home pass; and at every size
+    and in both dimensions the fp64 reference leaves no body without an acceleration."""
+    for pad in sym_probe.PADS:
+        n = sym_probe.body_count(pad)
+        assert (n + 4095) // 4096 * 4096 == pad and n % 4096 != 0 and (pad % 8192 == 0 or n > pad - 4096)
+        heavy = sym_probe.heavy_indices(pad, n)
+        assert len(set(heavy.tolist())) == heavy.size and 0 <= heavy.min() and heavy.max() == n - 1
+        cov = sym_probe.coverage(pad, n, heavy)
+        assert all(cov.values()), (pad, cov)
+    for pad, dim in ((pad, dim) for pad in sym_probe.PADS for dim in (3, 2)):
+        b, heavy = sym_probe.sparse_bodies(oracle, 500 + dim, pad, dim)
+        assert np.count_nonzero(b[:, -1]) == heavy.size and (b[heavy, -1] >= 1.0).all()
+        a, mag = sym_probe.reference(b, heavy)
+        norm = np.sqrt((a * a).sum(axis=1))
+        assert np.isfinite(a).all() and (norm > 0).all() and (mag >= norm * (1 - 1e-12)).all()
+        # the oracle's own rows of the same system: F_i = -(G m_i) a_i, so only the heavy rows carry a force
+        rows = heavy[:8]
+        want = oracle.force_rows_omp_2(b, rows)
+        got = -oracle.G * b[rows, -1:] * a[rows]
+        assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max()
+        print(f"pad={pad} D={dim}: {heavy.size} heavy bodies, share of bodies with kappa > 4: {float((mag > 4.0 * norm).mean()):.4f}")
 
 
 def test_summation_model_of_both_sides_at_65536_bodies(tmp_path, oracle):
