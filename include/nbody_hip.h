@@ -224,6 +224,38 @@ int nbx_leaf_plan_get_cells(nbx_leaf_plan* plan, double* mass_out, double* com_o
  * 0 otherwise); kernel_ms of the evaluation itself keeps meaning the near-field pair kernel.  Any pointer may be NULL. */
 int nbx_leaf_plan_cell_info(nbx_leaf_plan* plan, size_t* n_cells, size_t* far_entries, float* moments_ms, float* far_ms);
 
+/* ---- the order of the far field ---------------------------------------------------------------------------------------------
+ * NBX_FAR_MONOPOLE (every plan's order until told otherwise): a far cell attracts as one pseudo-body, as described above.
+ * NBX_FAR_QUADRUPOLE adds the second-order term of the expansion of the cell's bodies about its centre of mass (the first-order
+ * term, the dipole, vanishes there).  The law is m d / r^4 per unit target mass, one power of r steeper than Newton's; d / r^4 is
+ * not the gradient of a harmonic function in 3D, so the textbook traceless quadrupole does not apply and the FULL symmetric second
+ * moment is used:
+ *   moments: Q_ab = sum m_j s_a s_b, s = p_j - com_c, over the bodies of the cell's leaves, fp64 from the fp32 slot values in the
+ *       parallel-axis form -- per leaf about the leaf's own centre of mass, per cell sum_l [ Q_l + M_l (c_l - c)(c_l - c)^T ] --
+ *       so that nothing cancels; fixed order, no atomics, recomputed in every evaluation like M_c and com_c.  Stored and returned
+ *       in the order xx, yy, zz, xy, xz, yz (3D) or xx, yy, xy (2D).
+ *   term: with R = com_c - p_i, r^2 = |R|^2, q = Q / M_c, cell c adds to body i's sum
+ *           (M_c / r^4) [ R (1 - 2 tr(q) / r^2 + 12 R^T q R / r^4) - 4 q R / r^2 ]
+ *       -- the first R in the bracket is the monopole term, the rest the correction; the same formula holds in 2D with 2 x 2 q.
+ *       q is fp32 on the device (48 bytes per cell with the pseudo-body in 3D, 32 in 2D).  Sign and G m_i are the law's, as for
+ *       the monopole; where the law's rule below its threshold skips or softens the pair with the pseudo-body, the correction of
+ *       that pair is dropped.
+ *   fallback: a cell with M_c == 0, or one for which any entry of q is not finite in fp32 (masses of mixed sign with M_c near 0),
+ *       attracts as its monopole alone.  Masses of mixed sign within a cell are outside what the order's claims cover: the
+ *       expansion's error is then not bounded by the cell's size, and a q that is finite in fp32 but enormous (M_c near 0) can
+ *       still overflow inside the term; with masses of one sign |q| is bounded by the cell's extent squared and nothing overflows.
+ * nbx_leaf_plan_set_far_order: waits for the plan's last evaluation; NBX_ERR_INVALID for a null plan or an unknown order (the plan
+ * keeps its order).  May be called before or after nbx_leaf_plan_set_cells or an octree build; the order is the plan's and
+ * survives set_cells, rebuild_octree and step_octree.  A plan that stays at NBX_FAR_MONOPOLE allocates nothing for second moments
+ * and evaluates bit for bit as before. */
+enum { NBX_FAR_MONOPOLE = 0, NBX_FAR_QUADRUPOLE = 1 };
+int nbx_leaf_plan_set_far_order(nbx_leaf_plan* plan, int order);
+int nbx_leaf_plan_get_far_order(const nbx_leaf_plan* plan, int* order);
+/* Central second moments Q (not q) of the LAST evaluation as the far pass used them, before the division by M_c and the fp32
+ * rounding: q_out[n_cells][dim (dim + 1) / 2] in the order above (a massless cell: zeros).  Synchronises.  NBX_ERR_STATE on a plan
+ * at NBX_FAR_MONOPOLE and before the first evaluation at NBX_FAR_QUADRUPOLE with these cells; a plan without cells writes nothing. */
+int nbx_leaf_plan_get_cell_quadrupoles(nbx_leaf_plan* plan, double* q_out);
+
 /* ---- the octree built on the device ---------------------------------------------------------------
  * A fixed-depth octree (quadtree in 2D) over the bodies RESIDENT in a single-shard context, with the near and far lists of a
  * Barnes-Hut walk with opening angle theta (octree.cpp:129-151's test on grid boxes): the tree, both lists, the plan's layout and

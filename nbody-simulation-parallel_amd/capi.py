@@ -53,6 +53,9 @@ ABI = [
     ("nbx_leaf_plan_set_cells", _i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("nbx_leaf_plan_get_cells", _i, [_vp, _vp, _vp]),
     ("nbx_leaf_plan_cell_info", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _pf, _pf]),
+    ("nbx_leaf_plan_set_far_order", _i, [_vp, _i]),
+    ("nbx_leaf_plan_get_far_order", _i, [_vp, _pi]),
+    ("nbx_leaf_plan_get_cell_quadrupoles", _i, [_vp, _vp]),
     ("nbx_leaf_plan_create_octree", _i, [_c.POINTER(_vp), _vp, _i, _d]),
     ("nbx_leaf_plan_create_octree_adaptive", _i, [_c.POINTER(_vp), _vp, _i, _i, _d]),
     ("nbx_leaf_plan_rebuild_octree", _i, [_vp, _vp]),
@@ -262,6 +265,7 @@ def leapfrog_hip_n_body(bodies: np.ndarray, dt: float, nsteps: int, G: float = R
 
 
 LAW_BRUTE, LAW_TREE_LEAF, LAW_FMM_P2P = 0, 1, 2
+FAR_MONOPOLE, FAR_QUADRUPOLE = 0, 1
 FORCE_LAW_REFERENCE, FORCE_LAW_NEWTON = 0, 1
 
 
@@ -431,6 +435,25 @@ class LeafPlan:
         a, b, m, f = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_float(0.0), ctypes.c_float(0.0)
         self._ck(self.lib.nbx_leaf_plan_cell_info(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(m), ctypes.byref(f)), "nbx_leaf_plan_cell_info")
         return a.value, b.value, m.value, f.value
+
+    def set_far_order(self, order: int):
+        """FAR_MONOPOLE (every plan's start) or FAR_QUADRUPOLE: the far cells' second-order term on top of their pseudo-bodies
+        (nbx_leaf_plan_set_far_order).  The order is the plan's: it survives set_cells and octree rebuilds."""
+        self._ck(self.lib.nbx_leaf_plan_set_far_order(self.h, int(order)), "nbx_leaf_plan_set_far_order")
+
+    @property
+    def far_order(self) -> int:
+        v = ctypes.c_int(-1)
+        self._ck(self.lib.nbx_leaf_plan_get_far_order(self.h, ctypes.byref(v)), "nbx_leaf_plan_get_far_order")
+        return v.value
+
+    def get_cell_quadrupoles(self) -> np.ndarray:
+        """Q[n_cells, dim (dim + 1) / 2]: the cells' central second moments of the last evaluation at FAR_QUADRUPOLE, fp64, in the
+        order xx, yy, zz, xy, xz, yz (3D) or xx, yy, xy (2D) (nbx_leaf_plan_get_cell_quadrupoles)."""
+        n_cells = self.cell_info()[0]
+        q = np.zeros((n_cells, self.dim * (self.dim + 1) // 2), dtype=np.float64)
+        self._ck(self.lib.nbx_leaf_plan_get_cell_quadrupoles(self.h, q.ctypes.data if n_cells else None), "nbx_leaf_plan_get_cell_quadrupoles")
+        return q
 
     def time_kernel(self, law: int, reps: int) -> float:
         """Measurement: mean ms of the second half of `reps` back-to-back launches of the pair kernel."""

@@ -99,11 +99,21 @@ struct FarDevice {
     double* cell_mass = nullptr;           // [n_cells]       fp64 moments as the far pass used them, before the fp32 rounding
     double* cell_com = nullptr;            // [n_cells][dim]
     float4* cell_rec = nullptr;            // [n_cells] {x, y, z, M} fp32: the pseudo-bodies
+    // ---- order 1 (NBX_FAR_QUADRUPOLE) only; a plan at order 0 leaves all of it null and its passes never look ----
+    int order = 0;
+    double* leaf_quad = nullptr;           // [n_leaves][6]: central second moments of a leaf about its OWN centre of mass (3D order; 2D uses xx, yy, xy)
+    double* cell_quad = nullptr;           // [n_cells][dim (dim + 1) / 2] fp64 Q as the far pass used them, before the division by M and the fp32 rounding
+    float4* cell_qrec = nullptr;           // [n_cells][quad_rec_vecs(dim)] fp32 q = Q / M and its trace, next to cell_rec
 };
 
-// per-leaf moments, then every cell's (fixed summation order, no atomics)
+// The fp32 record of a cell's second moments, q = Q / M (all zeros: the cell attracts as its monopole alone):
+//   3D: {xx, yy, zz, xy}, {xz, yz, tr q, 0} -- with cell_rec 48 bytes per cell, three 16-byte loads;   2D: {xx, yy, xy, tr q} -- 32 bytes.
+constexpr uint32_t quad_rec_vecs(int dim) { return dim == 3 ? 2u : 1u; }
+constexpr uint32_t quad_count(int dim) { return (uint32_t)(dim * (dim + 1) / 2); }
+
+// per-leaf moments, then every cell's (fixed summation order, no atomics); at d.order == 1 the second moments behind them
 hipError_t enqueue_moments(const FarDevice& d, int dim, hipStream_t s);
-// the far terms of every target, added into d.sums
+// the far terms of every target, added into d.sums (d.order: monopoles, or monopoles + the second-order term)
 hipError_t enqueue_far(const FarDevice& d, int dim, int law, hipStream_t s);
 
 }  // namespace nbx_far

@@ -11,6 +11,13 @@
 //    the leaf range and meet in an LDS tree.
 //  Both write the fp64 moments (for nbx_leaf_plan_get_cells) and the 16-byte fp32 pseudo-body {x, y, z, M}; a cell of mass 0 becomes
 //  the pair kernels' pad body (massless, far away): its terms are exact zeros, never NaN (bvh.cpp:225 guards the same case).
+//  At order 1 (NBX_FAR_QUADRUPOLE) three more kernels of the same shapes follow, for the central second moments Q_ab = sum m s_a s_b,
+//  s = p - com, in the parallel-axis form (no term cancels; sum m x x^T - M c c^T is never formed):
+//  * far_leaf_quad_kernel: Q_l about the leaf's OWN centre of mass, kLeafLanes lanes per leaf, the same xor tree;
+//  * far_small_cells_quad_kernel / far_big_cells_quad_kernel: Q = sum_l [ Q_l + M_l (c_l - c)(c_l - c)^T ] over the cell's leaves, c the
+//    cell's centre of mass that the kernels above have just written.
+//  They write Q in fp64 (nbx_leaf_plan_get_cell_quadrupoles) and the fp32 record q = Q / M with its trace (leaf_far.h); the record is all
+//  zeros -- the cell then attracts as its monopole alone -- when M == 0 or when any entry of q is not finite in fp32.
 // Far pass: one wave64 per FarBlock (<= 64 targets of one leaf).  The wave walks the leaf's far list in tiles of kFarTile entries:
 //  lanes load the indices coalesced and gather the 16-byte records (L2 hits: neighbouring leaves name the same cells) through
 //  registers into LDS (two layouts, see far_kernel); a target is shared by P = min(64 / targets, kFarMaxLanes) lanes, lane group g takes
@@ -20,6 +27,14 @@
 //  The law's special cases are applied per pair with leaf_weight (leaf_law.h): the pair kernels' unguarded form needs every source mass
 //  below 1.7e10 (m / kTiny^2 finite for a coincident source), and a cell's mass is not a body's: at N = 2^20 with the reference's masses a
 //  child of the root weighs 6.5e12.
+//  ORDER 1 adds the second-order term of the expansion of sum m_j (R + s_j) / |R + s_j|^4 about the centre of mass (the dipole vanishes):
+//      (M / r^4) [ R (1 - 2 tr(q) / r^2 + 12 R^T q R / r^4) - 4 q R / r^2 ],   R = com - p_i, r^2 = |R|^2, q = Q / M.
+//  The law is one power of r steeper than Newton's, d / r^4 is not a harmonic function's gradient in 3D: the full symmetric q is needed,
+//  not the traceless one.  Evaluated with u = R / r^2 (|u| = 1 / r: nothing overflows, a pad's 1e18 included): q u, u^T q u, the scalar
+//  1 + 12 u^T q u - 2 tr(q) / r^2, the direction scalar * R - 4 q u.  1 / r^2 is the reciprocal leaf_weight_ri took for the weight; where
+//  the law skips or softens the pair it is 0 and the term is the monopole's, bit for bit.  The q records ride in a second LDS tile
+//  (32 B per record in 3D, 16 B in 2D) in the same two layouts; everything else -- one wave per FarBlock, float2 arithmetic on two
+//  records, the fp64 flush, the lane groups meeting in LDS in group order, one writer per slot -- is the monopole pass's.
 #include "leaf_far.h"
 #include "leaf_law.h"
 
@@ -102,10 +117,124 @@ __global__ __launch_bounds__(kCellThreads) void far_big_cells_kernel(FarDevice d
     if (tid == 0u) write_cell(d, dim, c, red[0][0], red[1][0], red[2][0], red[3][0]);
 }
 
-template <int D, int LAW>
+// ---- order 1: central second moments.  Six running sums whatever the dimension (xx, yy, zz, xy, xz, yz; 2D leaves three at zero). ----
+struct Quad { double xx = 0.0, yy = 0.0, zz = 0.0, xy = 0.0, xz = 0.0, yz = 0.0; };
+
+__global__ __launch_bounds__(256) void far_leaf_quad_kernel(const float* __restrict__ xp, const uint32_t* __restrict__ unit_off, uint32_t n_leaves,
+                                                            int dim, const double* __restrict__ leaf_mom, double* __restrict__ leaf_quad) {
+    const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t l = gid / kLeafLanes, k = gid % kLeafLanes;
+    Quad q;
+    if (l < n_leaves) {
+        const double* __restrict__ mo = leaf_mom + (size_t)l * 4u;
+        const double m = mo[0];
+        // a massless leaf: every term below is an exact zero whatever the centre
+        const double cx = m != 0.0 ? mo[1] / m : 0.0, cy = m != 0.0 ? mo[2] / m : 0.0, cz = m != 0.0 ? mo[3] / m : 0.0;
+        const uint32_t lo = unit_off[l], hi = unit_off[l + 1];
+        for (uint32_t p = lo + k; p < hi; p += kLeafLanes) {
+            const float* __restrict__ o = xp + (size_t)(p >> 1) * 8u + (p & 1u);
+            const double w = (double)o[6];
+            if (w == 0.0) continue;                      // a pad slot sits at 1e18: 0 * 1e36 is still zero, but keep it out of the sums' way
+            const double sx = (double)o[0] - cx, sy = (double)o[2] - cy;
+            q.xx += w * sx * sx; q.yy += w * sy * sy; q.xy += w * sx * sy;
+            if (dim == 3) {
+                const double sz = (double)o[4] - cz;
+                q.zz += w * sz * sz; q.xz += w * sx * sz; q.yz += w * sy * sz;
+            }
+        }
+    }
+    for (unsigned d = 1; d < kLeafLanes; d <<= 1) {       // every lane of the wave takes part; the order is fixed
+        q.xx += __shfl_xor(q.xx, (int)d); q.yy += __shfl_xor(q.yy, (int)d); q.zz += __shfl_xor(q.zz, (int)d);
+        q.xy += __shfl_xor(q.xy, (int)d); q.xz += __shfl_xor(q.xz, (int)d); q.yz += __shfl_xor(q.yz, (int)d);
+    }
+    if (l < n_leaves && k == 0u) {
+        double* __restrict__ o = leaf_quad + (size_t)l * 6u;
+        o[0] = q.xx; o[1] = q.yy; o[2] = q.zz; o[3] = q.xy; o[4] = q.xz; o[5] = q.yz;
+    }
+}
+
+// leaf l's share of a cell's Q about the cell's centre (cx, cy, cz): its own Q_l plus M_l (c_l - c)(c_l - c)^T
+__device__ __forceinline__ void add_leaf_quad(Quad& a, const FarDevice& d, uint32_t l, double cx, double cy, double cz) {
+    const double* __restrict__ mo = d.leaf_mom + (size_t)l * 4u;
+    const double* __restrict__ lq = d.leaf_quad + (size_t)l * 6u;
+    const double m = mo[0];
+    double ex = 0.0, ey = 0.0, ez = 0.0;
+    if (m != 0.0) { ex = mo[1] / m - cx; ey = mo[2] / m - cy; ez = mo[3] / m - cz; }
+    a.xx += lq[0] + m * ex * ex; a.yy += lq[1] + m * ey * ey; a.zz += lq[2] + m * ez * ez;
+    a.xy += lq[3] + m * ex * ey; a.xz += lq[4] + m * ex * ez; a.yz += lq[5] + m * ey * ez;
+}
+
+__device__ __forceinline__ void write_cell_quad(const FarDevice& d, int dim, uint32_t c, const Quad& Q) {
+    const double M = d.cell_mass[c];
+    double* __restrict__ o = d.cell_quad + (size_t)c * quad_count(dim);
+    float q[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};               // xx, yy, zz, xy, xz, yz, tr
+    if (M != 0.0) {
+        const double src[7] = {Q.xx, Q.yy, Q.zz, Q.xy, Q.xz, Q.yz, Q.xx + Q.yy + Q.zz};
+        bool finite = true;
+        for (int k = 0; k < 7; ++k) {
+            q[k] = (float)(src[k] / M);
+            finite = finite && __builtin_isfinite(q[k]);
+        }
+        if (!finite)                                                  // mixed-sign masses, M near 0: the monopole alone, never a NaN
+            for (int k = 0; k < 7; ++k) q[k] = 0.f;
+    }
+    if (M == 0.0) {                                                   // a massless cell reports zeros (masses that cancel exactly included)
+        for (uint32_t k = 0; k < quad_count(dim); ++k) o[k] = 0.0;
+    } else if (dim == 3) {
+        o[0] = Q.xx; o[1] = Q.yy; o[2] = Q.zz; o[3] = Q.xy; o[4] = Q.xz; o[5] = Q.yz;
+    } else {
+        o[0] = Q.xx; o[1] = Q.yy; o[2] = Q.xy;
+    }
+    if (dim == 3) {
+        d.cell_qrec[(size_t)c * 2u] = make_float4(q[0], q[1], q[2], q[3]);
+        d.cell_qrec[(size_t)c * 2u + 1u] = make_float4(q[4], q[5], q[6], 0.f);
+    } else {
+        d.cell_qrec[c] = make_float4(q[0], q[1], q[3], q[6]);
+    }
+}
+
+__global__ __launch_bounds__(256) void far_small_cells_quad_kernel(FarDevice d, int dim) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= d.n_small) return;
+    const uint32_t c = d.small_cells[i];
+    const uint32_t lo = d.cell_first[c], n = d.cell_count[c];
+    const double cx = d.cell_com[(size_t)c * dim], cy = d.cell_com[(size_t)c * dim + 1], cz = dim == 3 ? d.cell_com[(size_t)c * dim + 2] : 0.0;
+    Quad Q;
+    for (uint32_t l = lo; l < lo + n; ++l) add_leaf_quad(Q, d, l, cx, cy, cz);
+    write_cell_quad(d, dim, c, Q);
+}
+
+__global__ __launch_bounds__(kCellThreads) void far_big_cells_quad_kernel(FarDevice d, int dim) {
+    __shared__ double red[6][kCellThreads];
+    const uint32_t c = d.big_cells[blockIdx.x];
+    const uint32_t lo = d.cell_first[c], n = d.cell_count[c];
+    const uint32_t tid = threadIdx.x;
+    const double cx = d.cell_com[(size_t)c * dim], cy = d.cell_com[(size_t)c * dim + 1], cz = dim == 3 ? d.cell_com[(size_t)c * dim + 2] : 0.0;
+    Quad Q;
+    for (uint32_t l = tid; l < n; l += kCellThreads) add_leaf_quad(Q, d, lo + l, cx, cy, cz);
+    red[0][tid] = Q.xx; red[1][tid] = Q.yy; red[2][tid] = Q.zz; red[3][tid] = Q.xy; red[4][tid] = Q.xz; red[5][tid] = Q.yz;
+    __syncthreads();
+    for (uint32_t h = kCellThreads / 2u; h >= 1u; h >>= 1) {
+        if (tid < h)
+            for (int k = 0; k < 6; ++k) red[k][tid] += red[k][tid + h];
+        __syncthreads();
+    }
+    if (tid == 0u) {
+        Q.xx = red[0][0]; Q.yy = red[1][0]; Q.zz = red[2][0]; Q.xy = red[3][0]; Q.xz = red[4][0]; Q.yz = red[5][0];
+        write_cell_quad(d, dim, c, Q);
+    }
+}
+
+template <int D, int LAW, int ORDER>
 __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
     __shared__ __attribute__((aligned(16))) float4 tile[kFarTile + kFarTilePad];
     __shared__ double osum[3][64];
+    constexpr unsigned QV = quad_rec_vecs(D);                    // float4s of a cell's q record (leaf_far.h)
+    float4* qtile = nullptr;
+    if constexpr (ORDER == 1) {
+        __shared__ __attribute__((aligned(16))) float4 qtile_lds[(kFarTile + kFarTilePad) * QV];
+        qtile = qtile_lds;
+    }
     const unsigned lane = threadIdx.x;
     const FarBlock b = d.blocks[blockIdx.x];
     const unsigned W = b.count;                                   // 1 .. 64 (plan_far)
@@ -133,6 +262,8 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
     static_assert(kPerLane == 4, "the gather names four registers");
     // the gather of a tile: indices coalesced, then the records they name (every index was checked against n_cells by validate_cells)
     float4 r0 = pad_rec, r1 = pad_rec, r2_ = pad_rec, r3 = pad_rec;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 qr[kPerLane][QV];                                      // ORDER 1: the q records of the same four entries
     auto gather = [&](const uint32_t base) {
         const uint32_t e0 = base + lane, e1 = e0 + 64u, e2 = e0 + 128u, e3 = e0 + 192u;
         const uint32_t c0 = e0 < b.far_n ? list[e0] : 0xffffffffu, c1 = e1 < b.far_n ? list[e1] : 0xffffffffu;
@@ -141,6 +272,13 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
         r1 = c1 != 0xffffffffu ? d.cell_rec[c1] : pad_rec;
         r2_ = c2 != 0xffffffffu ? d.cell_rec[c2] : pad_rec;
         r3 = c3 != 0xffffffffu ? d.cell_rec[c3] : pad_rec;
+        if constexpr (ORDER == 1) {
+            const uint32_t cs[kPerLane] = {c0, c1, c2, c3};
+#pragma unroll
+            for (unsigned j = 0; j < kPerLane; ++j)
+#pragma unroll
+                for (unsigned v = 0; v < QV; ++v) qr[j][v] = cs[j] != 0xffffffffu ? d.cell_qrec[(size_t)cs[j] * QV + v] : zero4;
+        }
     };
     gather(0u);
     float* const tile_f = reinterpret_cast<float*>(tile);
@@ -151,6 +289,47 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
     // records (6 more moves per two terms).  Measured at N = 2^20 (profiles/r6/far_field.txt): the pair layout took the pass at 32-body
     // leaves from 0.77 to 0.66 ms; at 4-body leaves the pair layout for every wave cost 1.37 -> 1.68 ms.
     const bool pair_layout = P <= 4u;                             // wave-uniform
+    float* const qtile_f = reinterpret_cast<float*>(qtile);
+    // ORDER 1: two terms with their q (see the head of the file); ri = 0 leaves exactly the monopole's fma
+    auto two_terms_quad = [&](const f2 sx2, const f2 sy2, const f2 sz2, const f2 sm2, const f2 qxx, const f2 qyy, const f2 qzz, const f2 qxy,
+                              const f2 qxz, const f2 qyz, const f2 qtr) {
+        if (pending + 2u > kFlushTerms) flush();
+        const f2 dx = sx2 - ix2, dy = sy2 - iy2;
+        const f2 dz = (D == 3) ? sz2 - iz2 : f2{0.f, 0.f};
+        f2 r2 = dx * dx;
+        r2 = __builtin_elementwise_fma(dy, dy, r2);
+        if (D == 3) r2 = __builtin_elementwise_fma(dz, dz, r2);
+        float ria, rib;
+        const f2 w = {leaf_weight_ri<D, LAW>(r2.x, sm2.x, dx.x, dy.x, dz.x, ria), leaf_weight_ri<D, LAW>(r2.y, sm2.y, dx.y, dy.y, dz.y, rib)};
+        const f2 ri = {ria, rib};
+        const f2 ux = dx * ri, uy = dy * ri;
+        f2 gx = qxx * ux, gy = qxy * ux, gz = {0.f, 0.f};        // g = q u
+        gx = __builtin_elementwise_fma(qxy, uy, gx);
+        gy = __builtin_elementwise_fma(qyy, uy, gy);
+        f2 uz = {0.f, 0.f};
+        if (D == 3) {
+            uz = dz * ri;
+            gx = __builtin_elementwise_fma(qxz, uz, gx);
+            gy = __builtin_elementwise_fma(qyz, uz, gy);
+            gz = qxz * ux;
+            gz = __builtin_elementwise_fma(qyz, uy, gz);
+            gz = __builtin_elementwise_fma(qzz, uz, gz);
+        }
+        f2 uqu = ux * gx;
+        uqu = __builtin_elementwise_fma(uy, gy, uqu);
+        if (D == 3) uqu = __builtin_elementwise_fma(uz, gz, uqu);
+        const f2 one = {1.f, 1.f}, twelve = {12.f, 12.f}, m2 = {-2.f, -2.f}, m4 = {-4.f, -4.f};
+        f2 sc = __builtin_elementwise_fma(m2 * qtr, ri, one);
+        sc = __builtin_elementwise_fma(twelve, uqu, sc);
+        const f2 vx = __builtin_elementwise_fma(sc, dx, m4 * gx), vy = __builtin_elementwise_fma(sc, dy, m4 * gy);
+        ax = __builtin_elementwise_fma(w, vx, ax);
+        ay = __builtin_elementwise_fma(w, vy, ay);
+        if (D == 3) {
+            const f2 vz = __builtin_elementwise_fma(sc, dz, m4 * gz);
+            az = __builtin_elementwise_fma(w, vz, az);
+        }
+        pending += 2u;
+    };
     auto two_terms = [&](const f2 sx2, const f2 sy2, const f2 sz2, const f2 sm2) {
         if (pending + 2u > kFlushTerms) flush();
         const f2 dx = sx2 - ix2, dy = sy2 - iy2;
@@ -175,9 +354,30 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
             };
             put(lane, r0); put(lane + 64u, r1); put(lane + 128u, r2_); put(lane + 192u, r3);
             put(kFarTile + lane, pad_rec);
+            if constexpr (ORDER == 1) {
+                // a pair of q records interleaved like the source pair: {xxa,xxb,yya,yyb},{zza,zzb,xya,xyb},{xza,xzb,yza,yzb},{tra,trb,-,-}
+                // in 3D, {xxa,xxb,yya,yyb},{xya,xyb,tra,trb} in 2D
+                auto putq = [&](const unsigned e, const float4 (&q)[QV]) {
+                    float* __restrict__ o = qtile_f + (e >> 1) * (8u * QV) + (e & 1u);
+                    o[0] = q[0].x; o[2] = q[0].y; o[4] = q[0].z; o[6] = q[0].w;
+                    if (QV == 2u) { o[8] = q[QV - 1u].x; o[10] = q[QV - 1u].y; o[12] = q[QV - 1u].z; }
+                };
+                float4 zq[QV];
+                for (unsigned v = 0; v < QV; ++v) zq[v] = zero4;
+                putq(lane, qr[0]); putq(lane + 64u, qr[1]); putq(lane + 128u, qr[2]); putq(lane + 192u, qr[3]);
+                putq(kFarTile + lane, zq);
+            }
         } else {
             tile[lane] = r0; tile[lane + 64u] = r1; tile[lane + 128u] = r2_; tile[lane + 192u] = r3;
             tile[kFarTile + lane] = pad_rec;
+            if constexpr (ORDER == 1) {
+#pragma unroll
+                for (unsigned v = 0; v < QV; ++v) {
+                    qtile[lane * QV + v] = qr[0][v]; qtile[(lane + 64u) * QV + v] = qr[1][v];
+                    qtile[(lane + 128u) * QV + v] = qr[2][v]; qtile[(lane + 192u) * QV + v] = qr[3][v];
+                    qtile[(kFarTile + lane) * QV + v] = zero4;
+                }
+            }
         }
         __syncthreads();
         if (base + kFarTile < b.far_n) gather(base + kFarTile);   // in flight while this tile is consumed
@@ -187,7 +387,37 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
         const unsigned pairs = (cur + 1u) >> 1;
         const unsigned T = pair_layout ? (((pairs + P - 1u) / P) | 1u) : ((((cur + P - 1u) / P) + 1u) >> 1);
         const float4* __restrict__ s = tile + 2u * g * T;
-        if (pair_layout) {
+        if constexpr (ORDER == 1) {
+            const float4* __restrict__ qs = qtile + 2u * QV * g * T;   // the same records' q: 2 QV float4 per pair in either layout
+            if (pair_layout) {
+                for (unsigned i = 0; i < T; ++i) {
+                    const float4 A = s[2u * i], B = s[2u * i + 1u];
+                    if (D == 3) {
+                        const float4 Q0 = qs[4u * i], Q1 = qs[4u * i + 1u], Q2 = qs[4u * i + 2u];
+                        const f2 Q3 = *reinterpret_cast<const f2*>(qs + 4u * i + 3u);
+                        two_terms_quad(f2{A.x, A.y}, f2{A.z, A.w}, f2{B.x, B.y}, f2{B.z, B.w}, f2{Q0.x, Q0.y}, f2{Q0.z, Q0.w}, f2{Q1.x, Q1.y},
+                                       f2{Q1.z, Q1.w}, f2{Q2.x, Q2.y}, f2{Q2.z, Q2.w}, Q3);
+                    } else {
+                        const float4 Q0 = qs[2u * i], Q1 = qs[2u * i + 1u];
+                        two_terms_quad(f2{A.x, A.y}, f2{A.z, A.w}, f2{B.x, B.y}, f2{B.z, B.w}, f2{Q0.x, Q0.y}, f2{Q0.z, Q0.w}, f2{0.f, 0.f},
+                                       f2{Q1.x, Q1.y}, f2{0.f, 0.f}, f2{0.f, 0.f}, f2{Q1.z, Q1.w});
+                    }
+                }
+            } else {
+                for (unsigned i = 0; i < T; ++i) {
+                    const float4 A = s[2u * i], B = s[2u * i + 1u];
+                    if (D == 3) {
+                        const float4 A0 = qs[4u * i], A1 = qs[4u * i + 1u], B0 = qs[4u * i + 2u], B1 = qs[4u * i + 3u];
+                        two_terms_quad(f2{A.x, B.x}, f2{A.y, B.y}, f2{A.z, B.z}, f2{A.w, B.w}, f2{A0.x, B0.x}, f2{A0.y, B0.y}, f2{A0.z, B0.z},
+                                       f2{A0.w, B0.w}, f2{A1.x, B1.x}, f2{A1.y, B1.y}, f2{A1.z, B1.z});
+                    } else {
+                        const float4 A0 = qs[2u * i], B0 = qs[2u * i + 1u];
+                        two_terms_quad(f2{A.x, B.x}, f2{A.y, B.y}, f2{A.z, B.z}, f2{A.w, B.w}, f2{A0.x, B0.x}, f2{A0.y, B0.y}, f2{0.f, 0.f},
+                                       f2{A0.z, B0.z}, f2{0.f, 0.f}, f2{0.f, 0.f}, f2{A0.w, B0.w});
+                    }
+                }
+            }
+        } else if (pair_layout) {
             for (unsigned i = 0; i < T; ++i) {
                 const float4 A = s[2u * i], B = s[2u * i + 1u];
                 two_terms(f2{A.x, A.y}, f2{A.z, A.w}, f2{B.x, B.y}, f2{B.z, B.w});
@@ -212,11 +442,13 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
 }
 
 typedef void (*FarKernel)(FarDevice);
-FarKernel pick_far(int dim, int law) {
-    static const FarKernel table[2][3] = {
-        {far_kernel<2, NBX_LAW_BRUTE>, far_kernel<2, NBX_LAW_TREE_LEAF>, far_kernel<2, NBX_LAW_FMM_P2P>},
-        {far_kernel<3, NBX_LAW_BRUTE>, far_kernel<3, NBX_LAW_TREE_LEAF>, far_kernel<3, NBX_LAW_FMM_P2P>}};
-    return table[dim - 2][law];
+FarKernel pick_far(int dim, int law, int order) {
+    static const FarKernel table[2][2][3] = {
+        {{far_kernel<2, NBX_LAW_BRUTE, 0>, far_kernel<2, NBX_LAW_TREE_LEAF, 0>, far_kernel<2, NBX_LAW_FMM_P2P, 0>},
+         {far_kernel<3, NBX_LAW_BRUTE, 0>, far_kernel<3, NBX_LAW_TREE_LEAF, 0>, far_kernel<3, NBX_LAW_FMM_P2P, 0>}},
+        {{far_kernel<2, NBX_LAW_BRUTE, 1>, far_kernel<2, NBX_LAW_TREE_LEAF, 1>, far_kernel<2, NBX_LAW_FMM_P2P, 1>},
+         {far_kernel<3, NBX_LAW_BRUTE, 1>, far_kernel<3, NBX_LAW_TREE_LEAF, 1>, far_kernel<3, NBX_LAW_FMM_P2P, 1>}}};
+    return table[order][dim - 2][law];
 }
 
 }  // namespace
@@ -231,13 +463,22 @@ hipError_t enqueue_moments(const FarDevice& d, int dim, hipStream_t s) {
     }
     if (d.n_small) hipLaunchKernelGGL(far_small_cells_kernel, dim3((d.n_small + 255u) / 256u), dim3(256), 0, s, d, dim);
     if (d.n_big) hipLaunchKernelGGL(far_big_cells_kernel, dim3(d.n_big), dim3(kCellThreads), 0, s, d, dim);
+    if (d.order == 1) {
+        if (d.n_leaves) {
+            const size_t lanes = (size_t)d.n_leaves * kLeafLanes;
+            hipLaunchKernelGGL(far_leaf_quad_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float*>(d.xp),
+                               d.unit_off, d.n_leaves, dim, d.leaf_mom, d.leaf_quad);
+        }
+        if (d.n_small) hipLaunchKernelGGL(far_small_cells_quad_kernel, dim3((d.n_small + 255u) / 256u), dim3(256), 0, s, d, dim);
+        if (d.n_big) hipLaunchKernelGGL(far_big_cells_quad_kernel, dim3(d.n_big), dim3(kCellThreads), 0, s, d, dim);
+    }
     return hipGetLastError();
 }
 
 hipError_t enqueue_far(const FarDevice& d, int dim, int law, hipStream_t s) {
     if (!d.n_blocks) return hipSuccess;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(pick_far(dim, law), dim3(d.n_blocks), dim3(64), 0, s, d);
+    hipLaunchKernelGGL(pick_far(dim, law, d.order == 1 ? 1 : 0), dim3(d.n_blocks), dim3(64), 0, s, d);
     return hipGetLastError();
 }
 

@@ -17,17 +17,19 @@ constexpr float kFar = 1.0e18f;                 // pad bodies: massless, r^2 ~ 1
 static_assert(kTreeSkipF < 9.0e-7f, "a target outside the close set (nbx_internal.h) has no non-zero r^2 below 9.5e-7: no law's special case can apply to it");
 
 #ifdef __HIPCC__
-// Weight of d = p_j - p_i in the law's sum for ONE pair, every special case included: m_j / r^4 for an ordinary pair.
+// Weight of d = p_j - p_i in the law's sum for ONE pair, every special case included: m_j / r^4 for an ordinary pair.  `ri` receives
+// the reciprocal the weight was made of, 1 / r^2, for the far field's second-order term (leaf_far_kernel.hip) -- or 0 where the law
+// skips or softens the pair: the correction of that pair is then dropped (every factor of it carries ri).
 template <int D, int LAW>
-__device__ __forceinline__ float leaf_weight(float r2, float mj, float dx, float dy, float dz) {
+__device__ __forceinline__ float leaf_weight_ri(float r2, float mj, float dx, float dy, float dz, float& ri) {
     if (LAW == NBX_LAW_BRUTE) {
         const float g = (r2 < nbx::kR2SkipF) ? __builtin_inff() : r2;           // methods.cpp:24
-        const float ri = __builtin_amdgcn_rcpf(g);
+        ri = __builtin_amdgcn_rcpf(g);
         return mj * ri * ri;
     } else if (LAW == NBX_LAW_TREE_LEAF) {
         // "same position" (every |d_k| <= 1e-9) implies r2 <= 3e-18 < 1e-9: one test covers both skips
         const float g = (r2 < kTreeSkipF) ? __builtin_inff() : r2;
-        const float ri = __builtin_amdgcn_rcpf(g);
+        ri = __builtin_amdgcn_rcpf(g);
         return mj * ri * ri;
     } else {
         if (r2 < kSmoothF) {   // rare: smoothed magnitude, unsmoothed direction (fmm_parlay.cpp:1010-1020, vector.h:93-97)
@@ -35,11 +37,18 @@ __device__ __forceinline__ float leaf_weight(float r2, float mj, float dx, float
             const float r2s = r2 + 1.0e-10f;                                                   // epsilon^2, epsilon = 1e-5
             const float mag = mj * __builtin_amdgcn_rcpf(r2s) * __builtin_amdgcn_rsqf(r2s);    // m / (r2s * sqrt(r2s))
             const float inv = (r2 < kNormZeroF) ? 0.0f : __builtin_amdgcn_rsqf(r2);               // normalized(): 0 below 1e-10
+            ri = 0.0f;
             return same ? 0.0f : mag * inv;
         }
-        const float ri = __builtin_amdgcn_rcpf(r2);
+        ri = __builtin_amdgcn_rcpf(r2);
         return mj * ri * ri;
     }
+}
+
+template <int D, int LAW>
+__device__ __forceinline__ float leaf_weight(float r2, float mj, float dx, float dy, float dz) {
+    float ri;
+    return leaf_weight_ri<D, LAW>(r2, mj, dx, dy, dz, ri);
 }
 #endif
 

@@ -891,6 +891,11 @@ struct nbx_leaf_plan {
     // set_cells, destroy) clears it; nbx_leaf_plan_get_cells and the far pass of nbx_leaf_plan_time_kernel rely on that.
     bool cells_evaluated = false;
     bool cells_timed = false;       // ... and it recorded the four events
+    // ---- the far field's order (nbx_leaf_plan_set_far_order): the plan's own, it outlives cells and rebuilds ----
+    int far_order = NBX_FAR_MONOPOLE;
+    bool quads_evaluated = false;   // the last evaluation with these cells ran at order 1: cell_quad holds its second moments
+    char* quad_arena = nullptr;     // leaf_quad, cell_quad, cell_qrec of the cells as they stand; never allocated at order 0
+    size_t quad_arena_bytes = 0;
     // ---- a structure built on the device (nbx_leaf_plan_create_octree; octree_device.h) ----
     bool octree = false;            // made by nbx_leaf_plan_create_octree
     bool octree_built = false;      // ... and its last build went through (a refused rebuild leaves nothing to evaluate)
@@ -1169,14 +1174,45 @@ int plan_launch_near(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
     return NBX_OK;
 }
 
-// The far field (leaf_far_kernel.hip): the far terms of the plan's cells ADDED to the sums the pair kernels wrote.
-int plan_launch_far(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
+// The second moments' arrays for the plan's cells at order 1 (one block, kept and reused while it fits; a plan at order 0 never gets
+// here with anything to do).  The caller has made sure that nothing on the device still uses the block: every caller has waited for
+// the plan's last evaluation.
+int plan_fit_quads(nbx_leaf_plan* p) {
+    nbx_far::FarDevice& f = p->far;
+    f.order = p->far_order;
+    f.leaf_quad = nullptr; f.cell_quad = nullptr; f.cell_qrec = nullptr;
+    p->quads_evaluated = false;
+    if (p->far_order != NBX_FAR_QUADRUPOLE || !f.n_cells) return NBX_OK;
+    const size_t sizes[3] = {(size_t)f.n_leaves * 6 * sizeof(double), (size_t)f.n_cells * nbx_far::quad_count(p->dim) * sizeof(double),
+                             (size_t)f.n_cells * nbx_far::quad_rec_vecs(p->dim) * sizeof(float4)};
+    size_t offs[3], total = 0;
+    for (int i = 0; i < 3; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
+    if (!p->quad_arena || p->quad_arena_bytes < total) {
+        if (p->quad_arena) park_arena(p->device, p->quad_arena, p->quad_arena_bytes);
+        p->quad_arena = nullptr;
+        p->quad_arena_bytes = 0;
+        f.order = NBX_FAR_MONOPOLE;                     // should the allocation fail, the cells stay consistent at order 0 ...
+        NBX_HIP_TRY(take_arena(p->device, total, &p->quad_arena, &p->quad_arena_bytes));
+        f.order = p->far_order;
+    }
+    f.leaf_quad = reinterpret_cast<double*>(p->quad_arena + offs[0]);
+    f.cell_quad = reinterpret_cast<double*>(p->quad_arena + offs[1]);
+    f.cell_qrec = reinterpret_cast<float4*>(p->quad_arena + offs[2]);
+    return NBX_OK;
+}
+
+// The far field (leaf_far_kernel.hip): the far terms of the plan's cells ADDED to the sums the pair kernels wrote.  `with_moments`:
+// this evaluation's moment pass ran just before (nbx_leaf_plan_time_kernel repeats the far pass on the last evaluation's).
+int plan_launch_far(nbx_leaf_plan* p, int law, hipStream_t s, bool timed, bool with_moments = true) {
     if (!p->far.n_cells) return NBX_OK;
+    nbx_far::FarDevice f = p->far;
+    if (!with_moments && !p->quads_evaluated) f.order = NBX_FAR_MONOPOLE;   // no second moments of these positions: the order the sums were made at
     if (timed) NBX_HIP_TRY(hipEventRecord(p->evf0, s));
-    NBX_HIP_TRY(nbx_far::enqueue_far(p->far, p->dim, law, s));
+    NBX_HIP_TRY(nbx_far::enqueue_far(f, p->dim, law, s));
     if (timed) NBX_HIP_TRY(hipEventRecord(p->evf1, s));
     p->cells_evaluated = true;
     p->cells_timed = timed;
+    if (with_moments) p->quads_evaluated = f.order == NBX_FAR_QUADRUPOLE;
     return NBX_OK;
 }
 
@@ -1341,8 +1377,14 @@ void plan_release_cells(nbx_leaf_plan* p, bool device_idle, bool events) {
     p->cell_arena_bytes = 0;
     p->far = nbx_far::FarDevice();
     p->far_entries = 0;
-    p->cells_evaluated = p->cells_timed = false;
+    p->cells_evaluated = p->cells_timed = p->quads_evaluated = false;
     if (events) {
+        if (p->quad_arena) {                           // destroy: the block of the second moments goes too (set_cells keeps it for the next cells)
+            if (device_idle) park_arena(p->device, p->quad_arena, p->quad_arena_bytes);
+            else (void)hipFree(p->quad_arena);
+            p->quad_arena = nullptr;
+            p->quad_arena_bytes = 0;
+        }
         hipEvent_t* const evs[4] = {&p->evm0, &p->evm1, &p->evf0, &p->evf1};
         for (hipEvent_t* e : evs) {
             if (*e) (void)hipEventDestroy(*e);
@@ -1371,7 +1413,7 @@ int plan_build_octree(nbx_leaf_plan* p, nbx_ctx* c) {
     if (int rc = plan_order_after_last(p, s)) return rc;
     p->octree_built = false;
     p->evaluated = false;
-    p->cells_evaluated = p->cells_timed = false;
+    p->cells_evaluated = p->cells_timed = p->quads_evaluated = false;
     p->far = nbx_far::FarDevice();
     p->far_entries = 0;
     const int dim = p->dim, depth = p->octree_depth;
@@ -1437,6 +1479,7 @@ int plan_build_octree(nbx_leaf_plan* p, nbx_ctx* c) {
         f.cell_com = reinterpret_cast<double*>(cells + offs[4]);
         f.cell_rec = reinterpret_cast<float4*>(cells + offs[5]);
         p->far_entries = (size_t)C.far_entries;
+        if (int rc = plan_fit_quads(p)) { p->far = nbx_far::FarDevice(); p->far_entries = 0; return rc; }   // the stream is idle (synchronised above)
     }
     // as create_plan leaves a new plan: the sums of slots no workgroup writes are zero, the pads massless and far away
     const size_t sum_bytes = (size_t)dim * p->pslots * sizeof(double);
@@ -1824,6 +1867,46 @@ int nbx_leaf_plan_set_cells(nbx_leaf_plan* p, const uint32_t* cell_first_leaf, c
     d.cell_com = reinterpret_cast<double*>(arena + offs[8]);
     d.cell_rec = reinterpret_cast<float4*>(arena + offs[9]);
     p->far_entries = fp.far_entries;
+    if ((rc = plan_fit_quads(p))) { plan_release_cells(p, true, false); return rc; }   // the plan's order holds for the new cells
+    return plan_mark_done(p, s);
+}
+
+int nbx_leaf_plan_set_far_order(nbx_leaf_plan* p, int order) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (order != NBX_FAR_MONOPOLE && order != NBX_FAR_QUADRUPOLE) return fail(NBX_ERR_INVALID, "order must be NBX_FAR_MONOPOLE or NBX_FAR_QUADRUPOLE");
+    DeviceScope scope;
+    int rc = plan_set_device(p);
+    if (rc) return rc;
+    hipStream_t s = p->stream;
+    if ((rc = plan_order_after_last(p, s))) return rc;
+    NBX_HIP_TRY(hipStreamSynchronize(s));               // the last evaluation is over: nothing reads the cells' records any more
+    if (order == p->far_order) return plan_mark_done(p, s);
+    const int before = p->far_order;
+    p->far_order = order;
+    if ((rc = plan_fit_quads(p))) { p->far_order = before; (void)plan_fit_quads(p); return rc; }
+    return plan_mark_done(p, s);
+}
+
+int nbx_leaf_plan_get_far_order(const nbx_leaf_plan* p, int* order) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (!order) return fail(NBX_ERR_INVALID, "order is null");
+    *order = p->far_order;
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_get_cell_quadrupoles(nbx_leaf_plan* p, double* q_out) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (p->far_order != NBX_FAR_QUADRUPOLE) return fail(NBX_ERR_STATE, "the plan's far order is NBX_FAR_MONOPOLE: no second moments are computed");
+    if (!p->far.n_cells) return NBX_OK;
+    if (!p->cells_evaluated || !p->quads_evaluated) return fail(NBX_ERR_STATE, "no evaluation at NBX_FAR_QUADRUPOLE since the cells were set");
+    if (!q_out) return fail(NBX_ERR_INVALID, "q_out is null");
+    DeviceScope scope;
+    int rc = plan_set_device(p);
+    if (rc) return rc;
+    hipStream_t s = p->stream;
+    if ((rc = plan_order_after_last(p, s))) return rc;
+    NBX_HIP_TRY(hipMemcpyAsync(q_out, p->far.cell_quad, (size_t)p->far.n_cells * nbx_far::quad_count(p->dim) * sizeof(double), hipMemcpyDeviceToHost, s));
+    NBX_HIP_TRY(hipStreamSynchronize(s));
     return plan_mark_done(p, s);
 }
 
@@ -1877,7 +1960,7 @@ int nbx_leaf_plan_time_kernel(nbx_leaf_plan* p, int law, int reps, float* mean_m
         if ((rc = plan_launch_near(p, law, s, false))) return rc;
     }
     NBX_HIP_TRY(hipEventRecord(p->ev1, s));
-    if (p->cells_evaluated && (rc = plan_launch_far(p, law, s, false))) return rc;   // the sums keep their far terms (the last evaluation's moments)
+    if (p->cells_evaluated && (rc = plan_launch_far(p, law, s, false, false))) return rc;   // the sums keep their far terms (the last evaluation's moments)
     NBX_HIP_TRY(hipStreamSynchronize(s));
     if (p->n_blocks || p->n_packs) NBX_HIP_TRY(hipEventElapsedTime(mean_ms, p->ev0, p->ev1));
     *mean_ms /= (float)(reps - timed_from);

@@ -110,6 +110,11 @@ void LeafPairSimulationHip<D>::download(std::vector<Body<D>>& bodies) {
     if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::download", rc);
 }
 template <int D>
+void LeafPairSimulationHip<D>::set_far_order(int order) {
+    const int rc = nbx_leaf_plan_set_far_order(plan_, order);
+    if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::set_far_order", rc);
+}
+template <int D>
 float LeafPairSimulationHip<D>::single_launch_ms(LeafLaw law, double G) {
     float ms = 0.0f;
     const int rc = nbx_leaf_plan_forces_ctx(plan_, ctx_, static_cast<int>(law), G, nullptr, &ms);
@@ -139,12 +144,13 @@ struct OctreeOnDevice {
     nbx_ctx* ctx = nullptr;
     nbx_leaf_plan* plan = nullptr;
     // leaf_capacity < 0: the fixed-depth tree (depth 0: barnes_hut_hip_depth); otherwise the adaptive one, depth = max_depth
-    OctreeOnDevice(const std::vector<Body<D>>& bodies, double theta, int depth, const char* where, int leaf_capacity = -1) {
+    OctreeOnDevice(const std::vector<Body<D>>& bodies, double theta, int depth, const char* where, int leaf_capacity = -1, int far_order = NBX_FAR_MONOPOLE) {
         const int device = leaf_device();
         int rc = nbx_ctx_create(&ctx, device, D, bodies.size(), 1, 0);
         if (!rc) rc = nbx_ctx_upload_bodies(ctx, bodies.data(), sizeof(Body<D>));
         if (!rc && leaf_capacity >= 0) rc = nbx_leaf_plan_create_octree_adaptive(&plan, ctx, depth, leaf_capacity, theta);
         else if (!rc) rc = nbx_leaf_plan_create_octree(&plan, ctx, depth > 0 ? depth : barnes_hut_hip_depth(bodies.size(), D), theta);
+        if (!rc && far_order != NBX_FAR_MONOPOLE) rc = nbx_leaf_plan_set_far_order(plan, far_order);
         if (rc != NBX_OK) {
             nbx_leaf_plan_destroy(plan);
             nbx_ctx_destroy(ctx);
@@ -159,19 +165,19 @@ struct OctreeOnDevice {
 }  // namespace
 
 template <int D>
-std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta, int depth) {
+std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta, int depth, int far_order) {
     std::vector<Vector<D>> forces(bodies.size());
     if (bodies.empty()) return forces;
-    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_n_body");
+    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_n_body", -1, far_order);
     const int rc = nbx_leaf_plan_forces_ctx(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, reinterpret_cast<double*>(forces.data()), nullptr);
     if (rc != NBX_OK) raise_leaf("barnes_hut_hip_n_body", rc);
     return forces;
 }
 
 template <int D>
-void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every) {
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order) {
     if (bodies.empty()) return;
-    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_steps");
+    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_steps", -1, far_order);
     int rc = nbx_leaf_plan_step_octree(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, dt, nsteps, rebuild_every);
     if (!rc) rc = nbx_ctx_download_bodies(tree.ctx, bodies.data(), sizeof(Body<D>));
     if (rc != NBX_OK) raise_leaf("barnes_hut_hip_steps", rc);
@@ -184,21 +190,21 @@ void check_capacity(int leaf_capacity, const char* where) {
 }  // namespace
 
 template <int D>
-std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth) {
+std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, int far_order) {
     check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_n_body");
     std::vector<Vector<D>> forces(bodies.size());
     if (bodies.empty()) return forces;
-    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_n_body", leaf_capacity);
+    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_n_body", leaf_capacity, far_order);
     const int rc = nbx_leaf_plan_forces_ctx(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, reinterpret_cast<double*>(forces.data()), nullptr);
     if (rc != NBX_OK) raise_leaf("barnes_hut_hip_adaptive_n_body", rc);
     return forces;
 }
 
 template <int D>
-void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every) {
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every, int far_order) {
     check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_steps");
     if (bodies.empty()) return;
-    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_steps", leaf_capacity);
+    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_steps", leaf_capacity, far_order);
     int rc = nbx_leaf_plan_step_octree(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, dt, nsteps, rebuild_every);
     if (!rc) rc = nbx_ctx_download_bodies(tree.ctx, bodies.data(), sizeof(Body<D>));
     if (rc != NBX_OK) raise_leaf("barnes_hut_hip_adaptive_steps", rc);
@@ -217,16 +223,16 @@ void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double t
     for (std::size_t l = 0; l < *n_leaves; ++l) *largest_leaf = std::max<std::size_t>(*largest_leaf, offsets[l + 1] - offsets[l]);
 }
 
-template std::vector<Vector<2>> barnes_hut_hip_adaptive_n_body<2>(const std::vector<Body<2>>&, double, int, int);
-template std::vector<Vector<3>> barnes_hut_hip_adaptive_n_body<3>(const std::vector<Body<3>>&, double, int, int);
-template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int);
-template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int);
+template std::vector<Vector<2>> barnes_hut_hip_adaptive_n_body<2>(const std::vector<Body<2>>&, double, int, int, int);
+template std::vector<Vector<3>> barnes_hut_hip_adaptive_n_body<3>(const std::vector<Body<3>>&, double, int, int, int);
+template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int);
+template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int);
 template void barnes_hut_hip_adaptive_leaves<2>(const std::vector<Body<2>>&, double, int, int, std::size_t*, std::size_t*);
 template void barnes_hut_hip_adaptive_leaves<3>(const std::vector<Body<3>>&, double, int, int, std::size_t*, std::size_t*);
-template std::vector<Vector<2>> barnes_hut_hip_n_body<2>(const std::vector<Body<2>>&, double, int);
-template std::vector<Vector<3>> barnes_hut_hip_n_body<3>(const std::vector<Body<3>>&, double, int);
-template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int);
-template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int);
+template std::vector<Vector<2>> barnes_hut_hip_n_body<2>(const std::vector<Body<2>>&, double, int, int);
+template std::vector<Vector<3>> barnes_hut_hip_n_body<3>(const std::vector<Body<3>>&, double, int, int);
+template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int);
+template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int);
 
 template <int D>
 LeafLists build_uniform_leaves(const std::vector<Body<D>>& bodies, int depth) {

@@ -57,6 +57,8 @@ public:
     void step(LeafLaw law, double G, double dt, int nsteps);
     void synchronize();   // waits for the steps queued so far
     void download(std::vector<Body<D>>& bodies);
+    // 0 (NBX_FAR_MONOPOLE, every object's start) or 1 (NBX_FAR_QUADRUPOLE): the far cells' second-order term (nbx_leaf_plan_set_far_order)
+    void set_far_order(int order);
     float single_launch_ms(LeafLaw law, double G);      // pair kernel of one evaluation
     float back_to_back_ms(LeafLaw law, int reps);      // measurement: mean of the second half of `reps` launches in a row
 private:
@@ -92,21 +94,23 @@ LeafLists build_adaptive_octree_cells(const std::vector<Body<D>>& bodies, int ma
 // forces out, a new tree per call (methods.cpp:377-401).  The bodies go to a context, the fixed-depth octree, its near and far
 // lists and the plan's layout are made there (nbx_leaf_plan_create_octree), one evaluation under the tree-leaf law with the
 // reference's G follows, and the forces come back.  depth = 0 picks the smallest depth with at most 16 bodies per cell on
-// average (barnes_hut_hip_depth), capped at 10.  Throws std::runtime_error on failure; no CPU fallback.
+// average (barnes_hut_hip_depth), capped at 10.  far_order (here and in the three calls below): 0 = NBX_FAR_MONOPOLE, the reference's
+// pseudo-bodies; 1 = NBX_FAR_QUADRUPOLE adds the cells' second-order term (nbx_leaf_plan_set_far_order).  Throws std::runtime_error on
+// failure; no CPU fallback.
 template <int D>
-std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta = 0.5, int depth = 0);
+std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta = 0.5, int depth = 0, int far_order = 0);
 int barnes_hut_hip_depth(std::size_t n_bodies, int dim);
 // nsteps x { rebuild the tree when step % rebuild_every == 0; forces; update_body_velocities; update_body_positions } on the device
 // (nbx_leaf_plan_step_octree), the bodies brought back at the end.
 template <int D>
-void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every = 1);
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every = 1, int far_order = 0);
 
 // The same two calls over the ADAPTIVE octree (nbx_leaf_plan_create_octree_adaptive): leaves of at most leaf_capacity bodies down to
 // max_depth.  The tree for inputs whose density varies -- a Plummer sphere's centre -- where a fixed depth leaves cells of thousands.
 template <int D>
-std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth = 10);
+std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth = 10, int far_order = 0);
 template <int D>
-void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every = 1);
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every = 1, int far_order = 0);
 // leaves and largest leaf of the adaptive tree the device builds from `bodies` (what nbody_sim --leaf-cap reports)
 template <int D>
 void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, std::size_t* n_leaves, std::size_t* largest_leaf);

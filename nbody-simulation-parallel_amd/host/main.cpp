@@ -53,6 +53,7 @@ struct Options {
     double theta = 0.5;             // --theta: opening angle of the `-m t` row (methods.h:47's default)
     int depth = 0;                  // --depth: octree depth of the `-m t` row (0: at most 16 bodies per cell on average)
     int leaf_cap = 0;               // --leaf-cap k > 0: `-m t` builds the adaptive octree (leaves of <= k bodies; --depth = max depth, default 10)
+    int far_order = 0;              // --far-order 1: `-m t` runs its rows again with quadrupole far cells (rows named ..._quad)
     double refine = -1.0;           // --refine tol: per-body relative tolerance of the HIP rows (mixed mode); 0 = plain fp32; < 0: library default (1e-5)
 };
 
@@ -270,69 +271,96 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
 
     // Barnes-Hut with the octree built on the device: `-m t`.  The whole call is timed, as the reference times barnes_hut_seq_n_body
     // (a new tree per call, methods.cpp:377-401): upload, tree, lists, layout, moments, near and far pass, forces back.
-    if (m.find('t') != std::string::npos && opt.leaf_cap > 0) {
-        // the adaptive tree: leaves of at most --leaf-cap bodies down to --depth levels
-        const int max_depth = opt.depth > 0 ? opt.depth : 10;
-        out << "Barnes-Hut on HIP (adaptive octree, at most " << opt.leaf_cap << " bodies per leaf down to depth " << max_depth << ", built on the device, theta "
-            << opt.theta << "):" << std::endl;
-        Forces forces;
-        const long long us = safely_execute(log, "BarnesHut_HIP_adaptive", [&] { forces = barnes_hut_hip_adaptive_n_body<D>(bodies, opt.theta, opt.leaf_cap, max_depth); return 0; });
-        if (us >= 0) {
-            const double seconds = static_cast<double>(us) / 1e6;
-            csv << "BarnesHut_HIP_adaptive," << n << "," << D;
-            write_time(csv, seconds);
-            if (opt.accuracy) csv << "," << std::fixed << std::setprecision(2) << compute_accuracy<D>(forces, reference);
-            csv << std::endl;
-            out << "Time taken: " << seconds << " s" << std::endl;
-            std::size_t n_leaves = 0, largest = 0;
-            if (safely_execute(log, "BarnesHut_HIP_adaptive_leaves", [&] { barnes_hut_hip_adaptive_leaves<D>(bodies, opt.theta, opt.leaf_cap, max_depth, &n_leaves, &largest); return 0; }) >= 0)
-                out << "Leaves: " << n_leaves << ", largest leaf: " << largest << " bodies" << std::endl;
-            if (opt.accuracy) out << "Accuracy: " << std::to_string(compute_accuracy<D>(forces, reference)) << "%" << std::endl;
-            print_validation_forces<D>(forces, n, log);
-            print_validation_forces<D>(forces, n, std::cout);
-            if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive.f64", forces);
-            if (opt.steps > 0) {
-                std::vector<Body<D>> state = bodies;
-                const long long step_us = safely_execute(log, "BarnesHut_HIP_adaptive_steps", [&] {
-                    barnes_hut_hip_adaptive_steps<D>(state, opt.theta, opt.leaf_cap, max_depth, opt.dt, opt.steps, 1);
-                    return 0;
-                });
-                if (step_us >= 0) {
-                    csv << "BarnesHut_HIP_adaptive_steps," << n << "," << D;
-                    write_time(csv, static_cast<double>(step_us) / 1e6);
-                    csv << std::endl;
-                    out << "Barnes-Hut on HIP (adaptive), " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
-                        << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
-                    if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive_steps.f64", state);
+    // --far-order 1 runs the rows a second time with the far cells' second-order term (NBX_FAR_QUADRUPOLE), `_quad` appended to their
+    // names; without the flag the rows, their names and their numbers are the monopole's alone.
+    // The reference's Accuracy(%) cannot show what the second-order term buys: it counts bodies with every component within 1 %, holds
+    // components below 1e-20 to an absolute 1e-9 (most of them at the reference's G), and the brute-force rows push where the tree law
+    // pulls.  With --far-order 1 both rows therefore also print the relative error |F + F_ref| / |F_ref| over all bodies.
+    auto print_relative_error = [&](const Forces& forces) {
+        std::vector<double> rel;
+        rel.reserve(forces.size());
+        for (std::size_t i = 0; i < forces.size(); ++i) {
+            double d2 = 0.0, f2 = 0.0;
+            for (int k = 0; k < D; ++k) {
+                d2 += (forces[i][k] + reference[i][k]) * (forces[i][k] + reference[i][k]);
+                f2 += reference[i][k] * reference[i][k];
+            }
+            if (f2 > 0.0) rel.push_back(std::sqrt(d2 / f2));
+        }
+        if (rel.empty()) return;
+        std::sort(rel.begin(), rel.end());
+        out << "Relative force error against the brute-force forces (tree law's sign): median " << std::scientific << std::setprecision(3)
+            << rel[rel.size() / 2] << ", 99th percentile " << rel[std::min(rel.size() - 1, rel.size() * 99 / 100)] << std::fixed
+            << std::setprecision(6) << std::endl;
+    };
+    for (int order = 0; order <= opt.far_order && m.find('t') != std::string::npos; ++order) {
+        const std::string quad = order ? "_quad" : "";
+        if (opt.leaf_cap > 0) {
+            // the adaptive tree: leaves of at most --leaf-cap bodies down to --depth levels
+            const int max_depth = opt.depth > 0 ? opt.depth : 10;
+            out << "Barnes-Hut on HIP (adaptive octree, at most " << opt.leaf_cap << " bodies per leaf down to depth " << max_depth << ", built on the device, theta "
+                << opt.theta << (order ? ", far cells with their second moments" : "") << "):" << std::endl;
+            Forces forces;
+            const long long us = safely_execute(log, "BarnesHut_HIP_adaptive" + quad, [&] { forces = barnes_hut_hip_adaptive_n_body<D>(bodies, opt.theta, opt.leaf_cap, max_depth, order); return 0; });
+            if (us >= 0) {
+                const double seconds = static_cast<double>(us) / 1e6;
+                csv << "BarnesHut_HIP_adaptive" << quad << "," << n << "," << D;
+                write_time(csv, seconds);
+                if (opt.accuracy) csv << "," << std::fixed << std::setprecision(2) << compute_accuracy<D>(forces, reference);
+                csv << std::endl;
+                out << "Time taken: " << seconds << " s" << std::endl;
+                std::size_t n_leaves = 0, largest = 0;
+                if (safely_execute(log, "BarnesHut_HIP_adaptive_leaves" + quad, [&] { barnes_hut_hip_adaptive_leaves<D>(bodies, opt.theta, opt.leaf_cap, max_depth, &n_leaves, &largest); return 0; }) >= 0)
+                    out << "Leaves: " << n_leaves << ", largest leaf: " << largest << " bodies" << std::endl;
+                if (opt.accuracy) out << "Accuracy: " << std::to_string(compute_accuracy<D>(forces, reference)) << "%" << std::endl;
+                if (opt.accuracy && opt.far_order > 0) print_relative_error(forces);
+                print_validation_forces<D>(forces, n, log);
+                print_validation_forces<D>(forces, n, std::cout);
+                if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive" + quad + ".f64", forces);
+                if (opt.steps > 0) {
+                    std::vector<Body<D>> state = bodies;
+                    const long long step_us = safely_execute(log, "BarnesHut_HIP_adaptive_steps" + quad, [&] {
+                        barnes_hut_hip_adaptive_steps<D>(state, opt.theta, opt.leaf_cap, max_depth, opt.dt, opt.steps, 1, order);
+                        return 0;
+                    });
+                    if (step_us >= 0) {
+                        csv << "BarnesHut_HIP_adaptive_steps" << quad << "," << n << "," << D;
+                        write_time(csv, static_cast<double>(step_us) / 1e6);
+                        csv << std::endl;
+                        out << "Barnes-Hut on HIP (adaptive), " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
+                            << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
+                        if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive_steps" + quad + ".f64", state);
+                    }
                 }
             }
-        }
-        out << std::endl;
-    } else if (m.find('t') != std::string::npos) {
-        const int depth = opt.depth > 0 ? opt.depth : barnes_hut_hip_depth(static_cast<std::size_t>(n), D);
-        out << "Barnes-Hut on HIP (octree of depth " << depth << " built on the device, theta " << opt.theta << "):" << std::endl;
-        Forces forces;
-        const long long us = safely_execute(log, "BarnesHut_HIP", [&] { forces = barnes_hut_hip_n_body<D>(bodies, opt.theta, depth); return 0; });
-        if (us >= 0) {
-            const double seconds = static_cast<double>(us) / 1e6;
-            csv << "BarnesHut_HIP," << n << "," << D;
-            write_time(csv, seconds);
-            if (opt.accuracy) csv << "," << std::fixed << std::setprecision(2) << compute_accuracy<D>(forces, reference);
-            csv << std::endl;
-            out << "Time taken: " << seconds << " s" << std::endl;
-            if (opt.accuracy) out << "Accuracy: " << std::to_string(compute_accuracy<D>(forces, reference)) << "%" << std::endl;
-            print_validation_forces<D>(forces, n, log);
-            print_validation_forces<D>(forces, n, std::cout);
-            if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP.f64", forces);
-            if (opt.steps > 0) {
-                std::vector<Body<D>> state = bodies;
-                const long long step_us = safely_execute(log, "BarnesHut_HIP_steps", [&] { barnes_hut_hip_steps<D>(state, opt.theta, depth, opt.dt, opt.steps, 1); return 0; });
-                if (step_us >= 0)
-                    out << "Barnes-Hut on HIP, " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
-                        << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
+            out << std::endl;
+        } else {
+            const int depth = opt.depth > 0 ? opt.depth : barnes_hut_hip_depth(static_cast<std::size_t>(n), D);
+            out << "Barnes-Hut on HIP (octree of depth " << depth << " built on the device, theta " << opt.theta << (order ? ", far cells with their second moments" : "") << "):" << std::endl;
+            Forces forces;
+            const long long us = safely_execute(log, "BarnesHut_HIP" + quad, [&] { forces = barnes_hut_hip_n_body<D>(bodies, opt.theta, depth, order); return 0; });
+            if (us >= 0) {
+                const double seconds = static_cast<double>(us) / 1e6;
+                csv << "BarnesHut_HIP" << quad << "," << n << "," << D;
+                write_time(csv, seconds);
+                if (opt.accuracy) csv << "," << std::fixed << std::setprecision(2) << compute_accuracy<D>(forces, reference);
+                csv << std::endl;
+                out << "Time taken: " << seconds << " s" << std::endl;
+                if (opt.accuracy) out << "Accuracy: " << std::to_string(compute_accuracy<D>(forces, reference)) << "%" << std::endl;
+                if (opt.accuracy && opt.far_order > 0) print_relative_error(forces);
+                print_validation_forces<D>(forces, n, log);
+                print_validation_forces<D>(forces, n, std::cout);
+                if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP" + quad + ".f64", forces);
+                if (opt.steps > 0) {
+                    std::vector<Body<D>> state = bodies;
+                    const long long step_us = safely_execute(log, "BarnesHut_HIP_steps" + quad, [&] { barnes_hut_hip_steps<D>(state, opt.theta, depth, opt.dt, opt.steps, 1, order); return 0; });
+                    if (step_us >= 0)
+                        out << "Barnes-Hut on HIP, " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
+                            << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
+                }
             }
+            out << std::endl;
         }
-        out << std::endl;
     }
 
     // Near-field (leaf-pair direct sums) of the tree codes on the device: `-m p`.  The tree methods themselves are out of
@@ -504,6 +532,7 @@ void usage(const char* argv0) {
               << "                      softened Newtonian law (extension; needs --softening; Plummer velocities then use --G)" << std::endl
               << "      --softening <eps> Plummer softening of the stepping loop's pair law (extension; default 0 = the reference's law)" << std::endl
               << "      --leaf-cap <k>  -m t builds the ADAPTIVE octree: leaves of at most k bodies, --depth the deepest level (default 10); 0: fixed depth" << std::endl
+              << "      --far-order <0|1> 1: -m t runs its rows again with the far cells' second moments (quadrupole term; rows named ..._quad)" << std::endl
               << "      --energy-every <k> Log total energy and |dE/E0| every k steps (potential matching the selected law)" << std::endl
               << "      --refine <tol>  Per-body relative tolerance of the HIP rows: fp32 for all bodies + fp64 re-evaluation of those whose" << std::endl
               << "                      fp32 sum cannot be trusted to <tol> (default 1e-5: every body within 1e-5 of the sequential reference);" << std::endl
@@ -561,6 +590,12 @@ int main(int argc, char* argv[]) {
             opt.depth = std::stoi(argv[++i]);
         } else if (arg == "--leaf-cap" && has_value) {
             opt.leaf_cap = std::stoi(argv[++i]);
+        } else if (arg == "--far-order" && has_value) {
+            opt.far_order = std::stoi(argv[++i]);
+            if (opt.far_order != 0 && opt.far_order != 1) {
+                std::cerr << "Error: --far-order must be 0 (monopole) or 1 (quadrupole)" << std::endl;
+                return 1;
+            }
         } else if (arg == "--G" && has_value) {
             opt.G = std::stod(argv[++i]);
         } else if (arg == "--energy-every" && has_value) {

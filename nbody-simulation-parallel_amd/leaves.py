@@ -350,3 +350,80 @@ def adaptive_octree_cells(bodies: np.ndarray, dim: int, max_depth: int, leaf_cap
     cell_first = np.concatenate([lv_first[L] for L in range(1, depth + 1)])
     cell_count = np.concatenate([lv_count[L] for L in range(1, depth + 1)])
     return (u32(leaf_offsets), u32(order), u32(list_offsets), u32(near_s), u32(cell_first), u32(cell_count), u32(far_offsets), u32(far_c))
+
+
+# ---- the far field's second-order term: the fp64 specification of NBX_FAR_QUADRUPOLE (include/nbody_hip.h) --------------------
+# Plain numpy, nothing shared with the device code: these are what the tests hold csrc/leaf_far_kernel.hip to.
+
+def _quad_pairs(dim: int):
+    """Index pairs (a, b) of the stored moments: xx, yy, zz, xy, xz, yz in 3D; xx, yy, xy in 2D."""
+    return ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)) if dim == 3 else ((0, 0), (1, 1), (0, 1))
+
+
+def cell_moments(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, cell_first_leaf, cell_leaf_count, dtype=np.float64):
+    """(M[n_cells], com[n_cells, dim], Q[n_cells, dim (dim + 1) / 2]) of cells given as leaf ranges: total mass, centre of mass and
+    the central second moments Q_ab = sum m_j s_a s_b, s = p_j - com, summed directly about the centre (nothing cancels), in `dtype`.
+    A cell without mass (empty, or every body massless) gives zeros."""
+    lo, lb = np.asarray(leaf_offsets, dtype=np.int64), np.asarray(leaf_bodies, dtype=np.int64)
+    cf, cc = np.asarray(cell_first_leaf, dtype=np.int64), np.asarray(cell_leaf_count, dtype=np.int64)
+    pairs = _quad_pairs(dim)
+    M, com, Q = np.zeros(cf.size, dtype=dtype), np.zeros((cf.size, dim), dtype=dtype), np.zeros((cf.size, len(pairs)), dtype=dtype)
+    x_all, m_all = np.asarray(bodies[:, :dim], dtype=dtype), np.asarray(bodies[:, -1], dtype=dtype)
+    for c in range(cf.size):
+        ids = lb[lo[cf[c]]:lo[cf[c] + cc[c]]]
+        m = m_all[ids]
+        M[c] = m.sum()
+        if M[c] == 0:
+            continue
+        com[c] = (m[:, None] * x_all[ids]).sum(axis=0) / M[c]
+        s = x_all[ids] - com[c]
+        for k, (a, b) in enumerate(pairs):
+            Q[c, k] = (m * s[:, a] * s[:, b]).sum()
+    return M, com, Q
+
+
+def far_correction(R: np.ndarray, M, Q: np.ndarray) -> np.ndarray:
+    """What a cell of mass M and central second moments Q (stored order) adds to the monopole term M R / r^4 for a target at
+    -R from its centre of mass (R = com - p_i), per unit G m_i:
+        (M / r^4) [ R (-2 tr(q) / r^2 + 12 R^T q R / r^4) - 4 q R / r^2 ],   q = Q / M.
+    R[..., dim], M[...], Q[..., dim (dim + 1) / 2] broadcast together; zeros where M == 0."""
+    R = np.asarray(R)
+    dim = R.shape[-1]
+    pairs = _quad_pairs(dim)
+    M = np.asarray(M, dtype=R.dtype)
+    Q = np.asarray(Q, dtype=R.dtype)
+    live = M != 0
+    q = Q / np.where(live, M, 1)[..., None]
+    r2 = (R * R).sum(axis=-1)
+    tr = q[..., 0] + q[..., 1] + (q[..., 2] if dim == 3 else 0)
+    qR = np.zeros(np.broadcast(R, q[..., :1]).shape, dtype=R.dtype)
+    for k, (a, b) in enumerate(pairs):
+        qR[..., a] += q[..., k] * R[..., b]
+        if a != b:
+            qR[..., b] += q[..., k] * R[..., a]
+    RqR = (R * qR).sum(axis=-1)
+    scalar = -2 * tr / r2 + 12 * RqR / r2 ** 2
+    out = (M / r2 ** 2)[..., None] * (R * scalar[..., None] - 4 * qR / r2[..., None])
+    return np.where(live[..., None], out, 0)
+
+
+def far_sums(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, cell_first_leaf, cell_leaf_count, far_offsets, far_cells,
+             order: int = 0, moments=None) -> np.ndarray:
+    """Every body's far sum per unit G m_i, fp64: sum over the cells c of its leaf's far list of M_c R / r^4 (order 0), plus
+    far_correction (order 1).  No special case of any law is applied: far pairs are far.  moments: cell_moments' result, if at hand."""
+    lo, lb = np.asarray(leaf_offsets, dtype=np.int64), np.asarray(leaf_bodies, dtype=np.int64)
+    fo, fc = np.asarray(far_offsets, dtype=np.int64), np.asarray(far_cells, dtype=np.int64)
+    M, com, Q = moments if moments is not None else cell_moments(bodies, dim, lo, lb, cell_first_leaf, cell_leaf_count)
+    out = np.zeros((bodies.shape[0], dim))
+    for t in range(lo.size - 1):
+        ids, c = lb[lo[t]:lo[t + 1]], fc[fo[t]:fo[t + 1]]
+        c = c[M[c] != 0]
+        if not ids.size or not c.size:
+            continue
+        R = com[None, c, :] - bodies[ids, None, :dim]
+        r2 = (R * R).sum(axis=2)
+        term = (M[c] / r2 ** 2)[..., None] * R
+        if order == 1:
+            term = term + far_correction(R, M[None, c], Q[None, c, :])
+        out[ids] = term.sum(axis=1)
+    return out

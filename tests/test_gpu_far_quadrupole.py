@@ -1,0 +1,510 @@
+"""GPU: the second-order term of a leaf plan's far field (nbx_leaf_plan_set_far_order(NBX_FAR_QUADRUPOLE), csrc/leaf_far_kernel.hip)
+through the C ABI, against its fp64 specification in nbody_amd.leaves (cell_moments, far_correction).
+
+Reference of the parity tests: the PINNED oracle on the augmented system of test_gpu_far_field.py (the bodies plus one pseudo-body per
+cell at its fp64 centre of mass, every target's far cells behind its near list), plus the law-signed G m_i sum_c C_c, where
+    C_c = (M_c / r^4) [ R (-2 t / r^2 + 12 R^T q R / r^4) - 4 q R / r^2 ],   R = com_c - p_i, q = Q_c / M_c, t = tr(q),
+is leaves.far_correction in fp64 from numpy moments.
+
+Tolerance: TOL_BACKWARD_SMALL_N S_i + E_i as there, with two additions.
+  S_i gains G |m_i| sum_c |C_c|: the correction's terms are summed in fp32 like every other term.
+  E_i, the effects the oracle run does not contain, is the rounding of the cell's record to fp32.  For the pseudo-body it is the
+  existing term: d / r^4 moved by eps_c = sqrt(D) 2^-23 |com_c|_inf changes by at most 5 eps_c / r^4 (the derivative of d / r^4 is
+  bounded by (1 + 4) / r^4).  The correction gets the same treatment, two powers of r further down.  Every mass in these tests is
+  >= 0, so q is positive semi-definite: ||q||_2 <= t and ||q||_F <= t.  Term by term, the derivative with respect to R of
+      -2 t R / r^6             is bounded by  2 (1 + 6) t / r^6       =  14 t / r^6,
+      12 R (R^T q R) / r^8     by            12 (1 + 2 + 8) t / r^6   = 132 t / r^6,
+      -4 q R / r^6             by             4 (1 + 6) t / r^6       =  28 t / r^6,
+  so moving the centre of mass by eps_c changes C_c by at most 174 M_c t eps_c / r^6.  C_c is linear in q; the record carries q's
+  entries and t rounded to fp32, u = 2^-24 each (+ 2^-40 for the device's fp64 moments differing from numpy's in their last bits), so
+  ||dq||_2 <= ||dq||_F <= u t and |dt| <= u t change C_c by at most M_c (2 + 12 + 4) u t / r^5.  Together
+      E_i += G |m_i| sum_c M_c t_c (174 eps_c / r^6 + 18 u / r^5).
+  Both additions are computed here in fp64; the largest E_i / S_i is printed with every comparison.
+"""
+import contextlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle_lib import KAPPA_WELL, TOL_BACKWARD_SMALL_N, TOL_REL
+from test_far_quadrupole_cpu import MIN_GAIN, longdouble_moments
+
+pytestmark = pytest.mark.gpu
+LAWS = ((0, "brute"), (1, "tree_leaf"), (2, "fmm_p2p"))
+NBX_ERR_INVALID, NBX_ERR_STATE = 1, 5
+U_Q = 2.0 ** -24 + 2.0 ** -40
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@contextlib.contextmanager
+def planner(which):
+    before = os.environ.get("NBODY_HIP_LEAF_PLANNER")
+    os.environ["NBODY_HIP_LEAF_PLANNER"] = which
+    try:
+        yield
+    finally:
+        if before is None:
+            del os.environ["NBODY_HIP_LEAF_PLANNER"]
+        else:
+            os.environ["NBODY_HIP_LEAF_PLANNER"] = before
+
+
+def augmented(b, dim, leaves, far, mass, com):
+    """The system the oracle sees: bodies + one pseudo-body per cell (a one-body leaf each), far cells behind every near list."""
+    lo, lb, so, ss = (np.asarray(a, dtype=np.int64) for a in leaves)
+    fo, fc = (np.asarray(a, dtype=np.int64) for a in far)
+    n, nl, ncell = b.shape[0], lo.size - 1, mass.size
+    pseudo = np.zeros((ncell, b.shape[1]))
+    pseudo[:, :dim] = np.where(mass[:, None] != 0.0, com, -1.0e9)          # a massless cell: anywhere away from the bodies
+    pseudo[:, -1] = mass
+    lo2 = np.concatenate([lo, lo[-1] + 1 + np.arange(ncell)])
+    lb2 = np.concatenate([lb, n + np.arange(ncell)])
+    near_n, far_n = np.diff(so), np.diff(fo)
+    so2 = np.concatenate([[0], np.cumsum(near_n + far_n), np.full(ncell, so[-1] + fo[-1])])
+    ss2 = np.empty(so[-1] + fo[-1], dtype=np.int64)
+    t_near, t_far = np.repeat(np.arange(nl), near_n), np.repeat(np.arange(nl), far_n)
+    ss2[so2[t_near] + (np.arange(so[-1]) - so[t_near])] = ss
+    ss2[so2[t_far] + near_n[t_far] + (np.arange(fo[-1]) - fo[t_far])] = nl + fc
+    u32 = lambda a: np.asarray(a, dtype=np.uint32)
+    return np.ascontiguousarray(np.vstack([b, pseudo])), (u32(lo2), u32(lb2), u32(so2), u32(ss2))
+
+
+def far_terms(nbx, b, dim, leaves, far, mom, G, min_sep=None):
+    """Per body: sum_c C_c (a vector, per unit G m_i), the S_i addition and E_i (monopole part + correction part) of the module
+    docstring; also checks that every far pair is farther apart than min_sep (when given)."""
+    mass, com, Q = mom
+    assert (b[:, -1] >= 0.0).all(), "the bound assumes a positive semi-definite q"
+    lo, lb = np.asarray(leaves[0], dtype=np.int64), np.asarray(leaves[1], dtype=np.int64)
+    fo, fc = np.asarray(far[0], dtype=np.int64), np.asarray(far[1], dtype=np.int64)
+    eps = np.sqrt(dim) * 2.0 ** -23 * np.abs(com).max(axis=1) if mass.size else np.zeros(0)
+    t = Q[:, :dim].sum(axis=1) / np.where(mass != 0.0, mass, 1.0)
+    n = b.shape[0]
+    C, S_add, E = np.zeros((n, dim)), np.zeros(n), np.zeros(n)
+    closest = np.inf
+    for tl in range(lo.size - 1):
+        ids, c = lb[lo[tl]:lo[tl + 1]], fc[fo[tl]:fo[tl + 1]]
+        c = c[mass[c] != 0.0]
+        if not ids.size or not c.size:
+            continue
+        R = com[None, c, :] - b[ids, None, :dim]
+        r2 = (R * R).sum(axis=2)
+        r = np.sqrt(r2)
+        closest = min(closest, float(r.min()))
+        corr = nbx.leaves.far_correction(R, mass[None, c], Q[None, c, :])
+        C[ids] = corr.sum(axis=1)
+        S_add[ids] = G * np.abs(b[ids, -1]) * np.sqrt((corr * corr).sum(axis=2)).sum(axis=1)
+        mono = 5.0 * mass[c] * eps[c] / r2 ** 2
+        quad = mass[c] * t[c] * (174.0 * eps[c] / r2 ** 3 + 18.0 * U_Q / (r2 ** 2 * r))
+        E[ids] = G * np.abs(b[ids, -1]) * (mono + quad).sum(axis=1)
+    if min_sep is not None:
+        assert closest > min_sep, f"a far pair is only {closest:.3e} apart (expected more than {min_sep:.3e})"
+    return C, S_add, E
+
+
+def assert_far_parity(f, ref, S, E, what):
+    assert f.shape == ref.shape and np.isfinite(f).all(), what
+    dF = np.sqrt(((f - ref) ** 2).sum(axis=1))
+    nF = np.sqrt((ref ** 2).sum(axis=1))
+    live = S > 0
+    assert not f[~live].any(), f"{what}: bodies without any counted pair must get exactly zero"
+    worst = float((dF[live] / (TOL_BACKWARD_SMALL_N * S[live] + E[live])).max()) if live.any() else 0.0
+    print(f"{what}: backward error / bound = {worst:.3f}, largest E_i / S_i = {float((E[live] / S[live]).max()) if live.any() else 0.0:.2e}")
+    assert (dF[live] <= TOL_BACKWARD_SMALL_N * S[live] + E[live]).all(), f"{what}: backward error {worst:.2f} x the bound"
+    well = live & (nF > 0) & (S <= KAPPA_WELL * nF)
+    if well.any():
+        rel = dF[well] / nF[well]
+        assert (rel <= TOL_REL + E[well] / nF[well]).all(), f"{what}: relative error {float(rel.max()):.3e} on well-conditioned bodies"
+
+
+def all_paths(nbx, b, dim, leaves, cells, far, law, G, what):
+    """Order 1 through host bodies, resident bodies, and sums left on the device followed by get_forces, both planners, the order set
+    before the cells (host planner) and after them (device planner): the same bits."""
+    n, f = b.shape[0], None
+    for which in ("host", "device"):
+        with planner(which), nbx.LeafPlan(n, dim, *leaves) as plan:
+            if which == "host":
+                plan.set_far_order(nbx.FAR_QUADRUPOLE)
+            plan.set_cells(*cells, *far)
+            if which == "device":
+                plan.set_far_order(nbx.FAR_QUADRUPOLE)
+            assert plan.far_order == 1
+            got = plan.forces(b, law, G)
+            if f is None:
+                f = got
+            assert np.array_equal(got, f), f"{what}: plan (host bodies, {which} planner)"
+            with nbx.Context(n, dim) as c:
+                c.upload(b)
+                assert np.array_equal(plan.forces_ctx(c, law, G), f), f"{what}: plan (resident bodies, {which} planner)"
+                plan.forces_ctx(c, law, G, fetch=False)
+                assert np.array_equal(plan.get_forces(), f), f"{what}: sums left on the device ({which} planner)"
+    return f
+
+
+def check(nbx, oracle, b, dim, leaves, cells, far, law, what, min_sep=None):
+    mom = nbx.leaves.cell_moments(b, dim, leaves[0], leaves[1], *cells)
+    f = all_paths(nbx, b, dim, leaves, cells, far, law, oracle.G, what)
+    b2, leaves2 = augmented(b, dim, leaves, far, mom[0], mom[1])
+    n = b.shape[0]
+    C, S_add, E = far_terms(nbx, b, dim, leaves, far, mom, oracle.G, min_sep)
+    signed_G = -oracle.G if law == 0 else oracle.G
+    ref = oracle.leaf_pair_forces(b2, leaves2, law)[:n] + signed_G * b[:, -1:] * C
+    S = oracle.leaf_pair_magnitude_sums(b2, leaves2, law)[:n] + S_add
+    assert_far_parity(f, ref, S, E, what)
+    return f, signed_G * b[:, -1:] * C
+
+
+def octree(nbx, b, dim, depth, theta):
+    r = nbx.leaves.octree_cells(b, dim, depth, theta)
+    return r[:4], r[4:6], r[6:8]
+
+
+def box_side(b, dim, depth):
+    return float(np.ptp(b[:, :dim], axis=0).max()) * 1.01 / (1 << depth)
+
+
+@pytest.mark.parametrize("law,name", LAWS)
+@pytest.mark.parametrize("dim,depth,theta", ((3, 3, 0.5), (3, 4, 0.7), (2, 4, 0.5)))
+def test_parity_with_the_specification(nbx, oracle, dim, depth, theta, law, name):
+    """The shapes of test_gpu_far_field.py at order 1; the correction itself must be far above the tolerance, or the test shows nothing."""
+    b = oracle.round_inputs_to_f32(oracle.generate(50 + dim, 20000, dim))
+    leaves, cells, far = octree(nbx, b, dim, depth, theta)
+    what = f"order 1, octree depth {depth} theta {theta} D={dim} law {name}"
+    f, corr = check(nbx, oracle, b, dim, leaves, cells, far, law, what, min_sep=box_side(b, dim, depth) / theta)
+    size = np.sqrt((corr ** 2).sum(axis=1)) / np.sqrt((f ** 2).sum(axis=1))
+    print(f"{what}: median |correction| / |F| = {float(np.median(size)):.2e}")
+    assert np.median(size) > 10 * TOL_BACKWARD_SMALL_N
+
+
+def test_every_way_in_gives_the_same_bits(nbx, oracle):
+    """The octree built on the device (from_octree, from_octree_adaptive) at order 1 against a plan made from the same eight arrays
+    on the host; the order set before the first evaluation, and on the host-array plan between set_cells and the evaluation."""
+    n, dim = 20000, 3
+    b = oracle.round_inputs_to_f32(oracle.generate(53, n, dim))
+    with nbx.Context(n, dim) as c:
+        c.upload(b)
+        for what, make in (("from_octree", lambda: nbx.LeafPlan.from_octree(c, 4, 0.5)),
+                           ("from_octree_adaptive", lambda: nbx.LeafPlan.from_octree_adaptive(c, 6, 24, 0.6))):
+            with make() as plan:
+                f0 = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)
+                plan.set_far_order(nbx.FAR_QUADRUPOLE)
+                f1 = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)
+                arrays = plan.structure()
+                q = plan.get_cell_quadrupoles()
+            assert not np.array_equal(f0, f1), what
+            with nbx.LeafPlan(n, dim, *arrays[:4]) as ref:
+                ref.set_cells(*arrays[4:])
+                assert np.array_equal(ref.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G), f0), f"{what}: order 0 on the host arrays"
+                ref.set_far_order(nbx.FAR_QUADRUPOLE)
+                assert np.array_equal(ref.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G), f1), f"{what}: order 1 on the host arrays"
+                assert np.array_equal(ref.forces(b, nbx.LAW_TREE_LEAF, oracle.G), f1), f"{what}: host bodies"
+                assert np.array_equal(ref.get_cell_quadrupoles(), q), f"{what}: the cells' second moments"
+
+
+def test_order_0_is_untouched(nbx, oracle):
+    """A plan after set_far_order(0), one that went 1 -> 0 (with an evaluation at 1 in between) and one never told anything give the
+    same bits; none of them hands out second moments."""
+    n, dim = 20000, 3
+    b = oracle.round_inputs_to_f32(oracle.generate(53, n, dim))
+    leaves, cells, far = octree(nbx, b, dim, 3, 0.5)
+    with nbx.LeafPlan(n, dim, *leaves) as never, nbx.LeafPlan(n, dim, *leaves) as told, nbx.LeafPlan(n, dim, *leaves) as back:
+        for p in (never, told, back):
+            p.set_cells(*cells, *far)
+        told.set_far_order(nbx.FAR_MONOPOLE)
+        back.set_far_order(nbx.FAR_QUADRUPOLE)
+        f1 = back.forces(b, 1, oracle.G)
+        assert back.get_cell_quadrupoles().shape == (cells[0].size, 6)
+        back.set_far_order(nbx.FAR_MONOPOLE)
+        f = never.forces(b, 1, oracle.G)
+        assert not np.array_equal(f1, f), "order 1 must change the forces"
+        for what, p in (("set_far_order(0)", told), ("1 -> 0", back), ("never told", never)):
+            assert p.far_order == 0
+            assert np.array_equal(p.forces(b, 1, oracle.G), f), what
+            with pytest.raises(nbx.NbxError) as e:
+                p.get_cell_quadrupoles()
+            assert e.value.status == NBX_ERR_STATE, what
+        # at order 1, before the first evaluation with these cells: NBX_ERR_STATE too
+        back.set_far_order(nbx.FAR_QUADRUPOLE)
+        with pytest.raises(nbx.NbxError) as e:
+            back.get_cell_quadrupoles()
+        assert e.value.status == NBX_ERR_STATE
+        assert np.array_equal(back.forces(b, 1, oracle.G), f1), "0 -> 1 again"
+
+
+FAR_LENGTHS = (1, 2, 255, 256, 257, 512, 513, 600)
+
+
+def _ragged(seed, sizes, dim, n_cells_region=40):
+    """Target leaves of the given sizes in one region, the cells' leaves in another at least 1e4 away.  Cells: nested, overlapping,
+    empty, covering only empty leaves, all-massless, one-body; far lists: empty, of every length in FAR_LENGTHS, repeated entries;
+    targets with a far list and no near list."""
+    rng = np.random.default_rng(seed)
+    sizes = np.asarray(sizes, dtype=np.int64)
+    src_sizes = rng.integers(0, 9, n_cells_region)
+    src_sizes[5:8] = 0                                               # three empty leaves in a row
+    src_sizes[0] = 1                                                 # a one-body leaf: a one-body cell below
+    all_sizes = np.concatenate([sizes, src_sizes])
+    n_in = int(all_sizes.sum())
+    n = n_in + 5                                                     # five bodies in no leaf
+    lo = np.concatenate([[0], np.cumsum(all_sizes)])
+    lb = rng.permutation(n)[:n_in]
+    is_target = np.zeros(n, dtype=bool)
+    is_target[lb[:int(sizes.sum())]] = True
+    b = np.zeros((n, 2 * dim + 1))
+    b[:, :dim] = rng.uniform(1.0, 1.0e3, (n, dim))
+    b[~is_target, 0] += 2.0e4                                        # the cells' region (and the bodies in no leaf)
+    b[:, -1] = rng.uniform(1.0, 1.0e8, n)
+    b = np.ascontiguousarray(b.astype(np.float32).astype(np.float64))
+    nt, nl = sizes.size, all_sizes.size
+    b[lb[lo[nt + 10]:lo[nt + 12]], -1] = 0.0                         # two massless source leaves
+    where = (np.arange(len(FAR_LENGTHS)) * 7 + 3) % nt                # the leaves whose far lists get the lengths of FAR_LENGTHS
+    near_n = rng.integers(0, 4, nt)
+    near_n[::7] = 0                                                  # targets with an empty near list
+    near_n[where] = 0                                                # ... these too: with far terms alone in S_i the bound is ~1/250 of the correction
+    so = np.concatenate([[0], np.cumsum(near_n), np.full(nl - nt, near_n.sum())])
+    ss = []
+    for t, k in enumerate(near_n):                                   # the leaf itself first, then other target leaves
+        ss += ([t] + list(rng.integers(0, nt, k - 1))) if k else []
+    ss = np.asarray(ss, dtype=np.int64)
+    cf, cc = [], []
+    for first in range(nt, nl):
+        for count in (1, 3, 11):
+            if first + count <= nl and rng.random() < 0.5:
+                cf.append(first); cc.append(count)
+    # everything; only empty leaves; count 0; all massless; two empty ones; the one-body cell
+    cf += [nt, nt + 5, nt + 5, nt + 10, nl, nt + 3, nt]; cc += [nl - nt, 3, 0, 2, 0, 0, 1]
+    cf, cc = np.array(cf), np.array(cc)
+    far_n = rng.integers(0, 60, nt)
+    far_n[::5] = 0
+    far_n[where] = FAR_LENGTHS
+    far_n[0] = 300                                                   # leaf 0: no near list (0 mod 7), a far list longer than a tile
+    fo = np.concatenate([[0], np.cumsum(far_n), np.full(nl - nt, far_n.sum())])
+    fc = rng.integers(0, cf.size, int(far_n.sum()))
+    fc[fo[3]:fo[3] + 1] = cf.size - 1                                # the one-body cell and the all-massless one on a far list for certain
+    fc[fo[0]:fo[0] + 2] = (cf.size - 4, cf.size - 1)
+    assert near_n[0] == 0 and far_n[0] > 0 and set(FAR_LENGTHS) <= set(int(v) for v in far_n)
+    u32 = lambda a: np.asarray(a, dtype=np.uint32)
+    return b, (u32(lo), u32(lb), u32(so), u32(ss)), (u32(cf), u32(cc)), (u32(fo), u32(fc))
+
+
+@pytest.mark.parametrize("dim", (3, 2))
+@pytest.mark.parametrize("shape", ("1..70", "packed small leaves"))
+def test_ragged_structures(nbx, oracle, dim, shape):
+    """Leaves of 1 to 70 bodies: every number of targets per wave and of lanes per target, both tile layouts; and many small leaves
+    (sixteen lanes per target, the record layout) -- with far lists of every length around the tile's size."""
+    sizes = {"1..70": np.arange(1, 71), "packed small leaves": np.tile(np.arange(1, 9), 12)}[shape]
+    b, leaves, cells, far = _ragged(7 + dim, sizes, dim)
+    for law, name in LAWS[1:]:
+        f, corr = check(nbx, oracle, b, dim, leaves, cells, far, law, f"order 1, ragged {shape} D={dim} law {name}", min_sep=1.0e4)
+        lo, lb, so = (np.asarray(a, dtype=np.int64) for a in leaves[:3])
+        alone = np.concatenate([lb[lo[t]:lo[t + 1]] for t in range(sizes.size) if so[t + 1] == so[t] and far[0][t + 1] > far[0][t]])
+        size = np.sqrt((corr[alone] ** 2).sum(axis=1)) / np.sqrt((f[alone] ** 2).sum(axis=1))
+        print(f"bodies with far terms alone: {alone.size}, median |correction| / |F| = {float(np.median(size)):.2e}")
+        assert np.median(size) > 10 * TOL_BACKWARD_SMALL_N, "the correction is too small here for the bound to see it"
+        out = np.setdiff1d(np.arange(b.shape[0]), leaves[1])
+        assert out.size == 5 and not f[out].any(), "bodies in no leaf get exactly zero"
+
+
+@pytest.mark.parametrize("dim,depth", ((3, 4), (2, 5)))
+def test_device_moments_against_longdouble(nbx, oracle, dim, depth):
+    """get_cell_quadrupoles against np.longdouble sums over each cell's own bodies: |dQ_ab| <= 2^-24 tr(Q) per cell, for cells summed
+    by one lane (<= 8 leaves) and by a workgroup; massless and empty cells report zeros."""
+    n = 20000
+    b = oracle.round_inputs_to_f32(oracle.generate(60 + dim, n, dim))
+    leaves, cells, far = octree(nbx, b, dim, depth, 0.5)
+    lo, lb = leaves[0].astype(np.int64), leaves[1].astype(np.int64)
+    b[lb[lo[3]:lo[5]], -1] = 0.0                                    # two massless leaves
+    nl = lo.size - 1
+    cf = np.concatenate([cells[0], [3, 4, 0, nl]]).astype(np.int64)     # an all-massless cell, another, an empty one, an empty one at the end
+    cc = np.concatenate([cells[1], [2, 1, 0, 0]]).astype(np.int64)
+    assert (cc <= 8).sum() > 100 and (cc > 8).sum() >= 2 ** dim, "cells summed by one lane and by a workgroup must both occur"
+    _, _, QL = longdouble_moments(b, dim, lo, lb, cf, cc)
+    with nbx.LeafPlan(n, dim, *leaves) as plan:
+        plan.set_far_order(nbx.FAR_QUADRUPOLE)
+        plan.set_cells(cf.astype(np.uint32), cc.astype(np.uint32), *far)
+        with pytest.raises(nbx.NbxError) as e:
+            plan.get_cell_quadrupoles()
+        assert e.value.status == NBX_ERR_STATE                      # before the first evaluation with these cells
+        plan.forces(b, 1, oracle.G)
+        q = plan.get_cell_quadrupoles()
+    assert q.shape == QL.shape and not q[-4:].any()
+    tr = QL[:, :dim].sum(axis=1)
+    err = np.abs(q - QL)
+    assert (err <= 2.0 ** -24 * tr[:, None]).all()
+    live = tr > 0
+    for kind, sel in (("one lane", live & (cc <= 8)), ("workgroup", live & (cc > 8))):
+        print(f"device second moments D={dim}, cells summed by {kind}: largest |dQ| / tr(Q) = {float((err[sel] / tr[sel, None]).max()):.2e} (bound {2.0 ** -24:.2e})")
+
+
+def test_stepping_at_order_1(nbx, oracle):
+    """plan.step and step_octree (rebuilding every step and every third) at order 1 equal the loop of single calls bit for bit over 4
+    steps, and differ from the same loop at order 0; the order survives rebuilds, a refused one included."""
+    n, dim, depth, theta, dt, steps = 20000, 3, 4, 0.5, 1.5, 4
+    law, G = nbx.LAW_TREE_LEAF, oracle.G * 1e26
+    b0 = oracle.round_inputs_to_f32(oracle.generate(304, n, dim))
+    b0[:, dim:2 * dim] *= 1000.0
+    for every in (0, 1, 3):
+        ga, gb, g0 = b0.copy(), b0.copy(), b0.copy()
+        with nbx.Context(n, dim) as ca, nbx.Context(n, dim) as cb, nbx.Context(n, dim) as c0:
+            for c in (ca, cb, c0):
+                c.upload(b0)
+            with nbx.LeafPlan.from_octree(ca, depth, theta) as pa, nbx.LeafPlan.from_octree(cb, depth, theta) as pb, \
+                    nbx.LeafPlan.from_octree(c0, depth, theta) as p0:
+                pa.set_far_order(nbx.FAR_QUADRUPOLE)
+                pb.set_far_order(nbx.FAR_QUADRUPOLE)
+                for k in range(steps):
+                    if every and k % every == 0:
+                        pa.rebuild(ca)
+                        assert pa.far_order == 1
+                    pa.forces_ctx(ca, law, G, fetch=False)
+                    pa.kick_drift(ca, dt)
+                if every:
+                    pb.step_octree(cb, law, G, dt, steps, every)
+                    p0.step_octree(c0, law, G, dt, steps, every)
+                else:
+                    pb.step(cb, law, G, dt, steps)
+                    p0.step(c0, law, G, dt, steps)
+                assert pb.far_order == 1 and p0.far_order == 0
+                ca.download(ga); cb.download(gb); c0.download(g0)
+                assert np.array_equal(ga, gb), f"bodies after {steps} steps, rebuilding every {every}"
+                assert np.array_equal(pa.get_forces(), pb.get_forces())
+                assert np.array_equal(pa.get_cell_quadrupoles(), pb.get_cell_quadrupoles())
+                assert not np.array_equal(gb[:, dim:2 * dim], g0[:, dim:2 * dim]), "order 1 must move the bodies differently"
+    # a refused rebuild, then a successful one: still order 1, and the forces are those of a fresh plan at order 1
+    with nbx.Context(n, dim) as c:
+        c.upload(b0)
+        with nbx.LeafPlan.from_octree(c, depth, theta) as plan, nbx.LeafPlan.from_octree(c, depth, theta) as fresh:
+            plan.set_far_order(nbx.FAR_QUADRUPOLE)
+            fresh.set_far_order(nbx.FAR_QUADRUPOLE)
+            want = fresh.forces_ctx(c, law, G)
+            bad = b0.copy()
+            bad[n // 2, 1] = float("nan")
+            c.upload(bad)
+            with pytest.raises(nbx.NbxError) as e:
+                plan.rebuild(c)
+            assert e.value.status == NBX_ERR_INVALID and plan.far_order == 1
+            c.upload(b0)
+            plan.rebuild(c)
+            assert plan.far_order == 1
+            assert np.array_equal(plan.forces_ctx(c, law, G), want)
+
+
+def test_accuracy_on_the_device(nbx, oracle):
+    """N = 32,768 generated bodies, depth 4, theta 0.5, 4,096 sampled rows against the oracle's all-pairs sums: the median and the
+    99th percentile of the relative error at order 1 are at least MIN_GAIN (test_far_quadrupole_cpu.py) times below order 0's.  A
+    Plummer sphere through the adaptive tree (capacity 32) is printed next to them."""
+    n, dim = 32768, 3
+    rows = np.sort(np.random.default_rng(11).choice(n, 4096, replace=False))
+
+    def errors(b, make):
+        ref = -oracle.force_rows_omp_2(b, rows)                     # brute force pushes (methods.cpp:131), the tree laws pull
+        out = []
+        with nbx.Context(n, dim) as c:
+            c.upload(b)
+            with make(c) as plan:
+                for order in (0, 1):
+                    plan.set_far_order(order)
+                    f = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)[rows]
+                    out.append(np.sqrt(((f - ref) ** 2).sum(axis=1)) / np.sqrt((ref ** 2).sum(axis=1)))
+        return out
+
+    b = oracle.round_inputs_to_f32(oracle.generate(81, n, dim))
+    e0, e1 = errors(b, lambda c: nbx.LeafPlan.from_octree(c, 4, 0.5))
+    gm, gp = float(np.median(e0) / np.median(e1)), float(np.percentile(e0, 99) / np.percentile(e1, 99))
+    print(f"uniform N={n} depth 4 theta 0.5: median {np.median(e0):.2e} -> {np.median(e1):.2e} ({gm:.1f}x), "
+          f"p99 {np.percentile(e0, 99):.2e} -> {np.percentile(e1, 99):.2e} ({gp:.1f}x)")
+    bp = oracle.round_inputs_to_f32(np.ascontiguousarray(nbx.plummer_bodies(n, dim, seed=3)))
+    p0, p1 = errors(bp, lambda c: nbx.LeafPlan.from_octree_adaptive(c, 10, 32, 0.5))
+    print(f"Plummer N={n} adaptive capacity 32 theta 0.5: median {np.median(p0):.2e} -> {np.median(p1):.2e} "
+          f"({float(np.median(p0) / np.median(p1)):.1f}x), p99 {np.percentile(p0, 99):.2e} -> {np.percentile(p1, 99):.2e} "
+          f"({float(np.percentile(p0, 99) / np.percentile(p1, 99)):.1f}x)")
+    assert gm >= MIN_GAIN and gp >= MIN_GAIN
+
+
+def test_refusals_and_the_fallback(nbx, oracle):
+    """An unknown order is NBX_ERR_INVALID and leaves the order as it was.  A cell whose masses sum to nearly nothing -- +1, -1 and
+    1e-30 a unit apart, so that q = Q / M overflows fp32 -- attracts as its monopole alone: finite forces, equal to order 0's."""
+    dim, G = 3, oracle.G
+    rng = np.random.default_rng(5)
+    nt = 6
+    b = np.zeros((nt + 3 + 4, 2 * dim + 1))
+    b[:nt, :dim] = rng.uniform(1.0, 2.0, (nt, dim))
+    b[:nt, -1] = rng.uniform(1.0, 10.0, nt)
+    b[nt:nt + 3, :dim] = ((100.0, 100.0, 100.0), (101.0, 100.5, 100.25), (100.5, 101.0, 100.75))
+    b[nt:nt + 3, -1] = (1.0, -1.0, 1.0e-30)
+    b[nt + 3:, :dim] = rng.uniform(200.0, 210.0, (4, dim))           # an ordinary cell beside it
+    b[nt + 3:, -1] = rng.uniform(1.0, 10.0, 4)
+    b = np.ascontiguousarray(b.astype(np.float32).astype(np.float64))
+    u32 = lambda a: np.asarray(a, dtype=np.uint32)
+    leaves = (u32([0, nt, nt + 3, nt + 7]), u32(np.arange(nt + 7)), u32([0, 1, 2, 3]), u32([0, 1, 2]))
+    cells = (u32([1, 2]), u32([1, 1]))
+    with nbx.LeafPlan(b.shape[0], dim, *leaves) as plan:
+        for order in (2, -1, 7):
+            with pytest.raises(nbx.NbxError) as e:
+                plan.set_far_order(order)
+            assert e.value.status == NBX_ERR_INVALID and plan.far_order == 0
+        plan.set_far_order(nbx.FAR_QUADRUPOLE)
+        with pytest.raises(nbx.NbxError) as e:
+            plan.set_far_order(2)
+        assert e.value.status == NBX_ERR_INVALID and plan.far_order == 1
+        got = {}
+        for what, far in (("both cells", (u32([0, 2, 2, 2]), u32([0, 1]))), ("the ordinary cell", (u32([0, 1, 1, 1]), u32([1])))):
+            plan.set_cells(*cells, *far)
+            for order in (0, 1):
+                plan.set_far_order(order)
+                got[what, order] = plan.forces(b, nbx.LAW_TREE_LEAF, G)
+                assert np.isfinite(got[what, order]).all(), (what, order)
+                if order == 1 and what == "both cells":
+                    mass, _ = plan.cells()
+                    Q = plan.get_cell_quadrupoles()
+                    assert 0.0 < mass[0] < 1.0e-29 and np.isfinite(Q).all()
+                    assert np.abs(Q[0] / mass[0]).max() > 3.5e38, "q of the cancelling cell must overflow fp32, or the test shows nothing"
+        # the cancelling cell adds the same at either order (its monopole); the ordinary cell's correction is there
+        d0 = got["both cells", 0] - got["the ordinary cell", 0]
+        d1 = got["both cells", 1] - got["the ordinary cell", 1]
+        assert np.array_equal(d0, d1)
+        assert not np.array_equal(got["the ordinary cell", 0][:nt], got["the ordinary cell", 1][:nt])
+
+
+def test_cpp_layer_and_harness(nbx, oracle, tmp_path):
+    """barnes_hut_hip_n_body<3>(bodies, theta, depth, NBX_FAR_QUADRUPOLE) (tests/far_quadrupole_cpp_check.cpp, built here) gives the
+    bits of the Python octree plan at order 1; nbody_sim -m t -a 1 --far-order 1 prints a BarnesHut_HIP_quad row more accurate than the
+    BarnesHut_HIP row of the same run (by the relative error printed with both; the reference's Accuracy(%) is blind to it, see below)."""
+    n, dim, theta, depth = 20000, 3, 0.5, 4
+    b = oracle.round_inputs_to_f32(oracle.generate(307, n, dim))
+    pkg = os.path.join(ROOT, "nbody-simulation-parallel_amd")
+    exe = str(tmp_path / "far_quadrupole_cpp_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "host"),
+                    os.path.join(ROOT, "tests", "far_quadrupole_cpp_check.cpp"), os.path.join(pkg, "host", "leaf_pairs_hip.cpp"), "-o", exe,
+                    "-L" + pkg, "-lnbody_hip", "-Wl,-rpath," + pkg], check=True, capture_output=True, text=True)
+    bodies, out = str(tmp_path / "bodies.f64"), str(tmp_path / "forces.f64")
+    np.ascontiguousarray(b).tofile(bodies)
+    p = subprocess.run([exe, "3", bodies, str(n), str(depth), repr(theta), out], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    with nbx.Context(n, dim) as c:
+        c.upload(b)
+        with nbx.LeafPlan.from_octree(c, depth, theta) as plan:
+            f0 = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)
+            plan.set_far_order(nbx.FAR_QUADRUPOLE)
+            f1 = plan.forces_ctx(c, nbx.LAW_TREE_LEAF, oracle.G)
+    got = np.fromfile(out).reshape(n, dim)
+    assert np.array_equal(got, f1) and not np.array_equal(got, f0)
+    sim = os.path.join(ROOT, "nbody_sim")
+    assert os.path.exists(sim)
+    p = subprocess.run([sim, "-N", "20000", "-m", "t", "-a", "1", "--far-order", "1"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    found = [os.path.join(d, f_) for d, _, files in os.walk(tmp_path) for f_ in files if f_.endswith(".csv")]
+    rows = {line.split(",")[0]: line.strip().split(",") for path in found for line in open(path) if line.startswith("BarnesHut_HIP")}
+    assert sorted(rows) == ["BarnesHut_HIP", "BarnesHut_HIP_quad"], p.stdout + p.stderr
+    acc = [float(line.split(":")[1].strip().rstrip("%")) for line in p.stdout.splitlines() if line.startswith("Accuracy:")]
+    err = [[float(v.split()[-1]) for v in line.split(":")[1].split(",")] for line in p.stdout.splitlines() if line.startswith("Relative force error")]
+    print(f"\nnbody_sim --far-order 1: Accuracy {acc} %, relative error (median, p99) {err}; rows {rows}")
+    # The Accuracy(%) column is the reference's metric: bodies with every component within 1 %, components below 1e-20 held to an
+    # absolute 1e-9, against brute-force forces of the opposite sign -- measured 92.665 % for both rows of this run, it cannot move.
+    # The figure that can is the relative error the harness prints under --far-order 1 for both rows.
+    assert len(acc) == 2 and 0.0 <= acc[0] <= acc[1] <= 100.0
+    assert len(err) == 2 and err[1][0] < err[0][0] and err[1][1] < err[0][1], "the _quad row must be the more accurate one"
+    # without the flag: the plain row alone, no new line
+    p = subprocess.run([sim, "-N", "20000", "-m", "t", "-a", "1"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "_quad" not in p.stdout and "Relative force error" not in p.stdout
