@@ -140,7 +140,9 @@ int nbx_leapfrog(void* bodies, size_t n, int dim, size_t body_stride_bytes,
  * refusal comes back with the layout's 64-byte summary).  kernel_ms (optional) receives the pair kernel's duration (hipEvent).
  * This one-shot form validates, lays out and uploads the structure on every call (2.4-3.1 ms at N = 2^20, 84 MB of it PCIe);
  * a tree code that evaluates its leaf sums every step from resident bodies uses the PLAN below. */
-enum { NBX_LAW_BRUTE = 0, NBX_LAW_TREE_LEAF = 1, NBX_LAW_FMM_P2P = 2 };
+/* NBX_LAW_NEWTON is the plan's fourth law (below, "softened Newtonian gravity on a plan"); this one-shot call has no plan to carry
+ * a softening length and refuses it with NBX_ERR_INVALID. */
+enum { NBX_LAW_BRUTE = 0, NBX_LAW_TREE_LEAF = 1, NBX_LAW_FMM_P2P = 2, NBX_LAW_NEWTON = 3 };
 int nbx_leaf_pair_forces(const void* bodies, size_t n, int dim, size_t body_stride_bytes,
                          const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves,
                          const uint32_t* list_offsets, const uint32_t* list_sources,
@@ -255,6 +257,31 @@ int nbx_leaf_plan_get_far_order(const nbx_leaf_plan* plan, int* order);
  * rounding: q_out[n_cells][dim (dim + 1) / 2] in the order above (a massless cell: zeros).  Synchronises.  NBX_ERR_STATE on a plan
  * at NBX_FAR_MONOPOLE and before the first evaluation at NBX_FAR_QUADRUPOLE with these cells; a plan without cells writes nothing. */
 int nbx_leaf_plan_get_cell_quadrupoles(nbx_leaf_plan* plan, double* q_out);
+
+/* ---- softened Newtonian gravity on a plan ------------------------------------------------------------------------------------
+ * NBX_LAW_NEWTON: the attractive Plummer-softened law of nbx_ctx_set_law(NBX_FORCE_LAW_NEWTON), evaluated through the plan -- near
+ * lists, far cells at either order, the step loops.  Per unit G m_i a source j adds
+ *       m_j d / (r^2 + epsilon^2)^(3/2),   d = p_j - p_i
+ * and F_i = +G m_i x the sum (the tree laws' sign).  Every pair counts: a body and itself, or two bodies at one position, give
+ * exactly 0 (d = 0, a finite weight); there is no threshold and no special case, so every wave runs the pair loop without a
+ * compare.  A far cell is a pseudo-body under the same formula; at NBX_FAR_QUADRUPOLE it adds the exact second-order term of the
+ * softened kernel with the same full q = Q / M_c the moment pass writes (rho^2 = r^2 + epsilon^2):
+ *       (M_c / rho^3) [ R (1 - (3/2) tr(q) / rho^2 + (15/2) R^T q R / rho^4) - 3 q R / rho^2 ]
+ * epsilon is the PLAN's (nbx_leaf_plan_set_softening; 0 until told otherwise): 0 or in [1e-6, 1e15], the context's range;
+ * NBX_ERR_INVALID outside it and for a null plan, the plan then keeps its value.  The call waits for the plan's last evaluation;
+ * the value survives set_cells, rebuild_octree and step_octree.  The three other laws never read it: their results are bit for
+ * bit those of a plan never told.
+ * An evaluation (nbx_leaf_plan_forces, _forces_ctx, _step, _step_octree, _time_kernel) under NBX_LAW_NEWTON returns, before anything
+ * is launched, NBX_ERR_STATE while epsilon is 0, and NBX_ERR_INVALID when max|m| / epsilon^3 -- the heaviest body's weight at zero
+ * distance -- is not a finite, normal fp32 number (the context's rule; the largest mass is what the context recorded at upload, or,
+ * for host bodies, found in one pass over the masses about to be copied).  RANGE: the pair terms are fp32; rho^-3 is formed as such in
+ * the packed waves of small leaves, so the terms keep fp32's precision for rho = sqrt(r^2 + epsilon^2) < 4.4e12 (rho^-3 a normal fp32
+ * number) and lose bits gradually beyond -- distances or softening lengths above that are accepted (the m / epsilon^3 rule is about the
+ * masses) but outside what the law's accuracy claims cover; the reference laws' 1 / r^4 meets the same limit at r = 3e9.
+ * The context's own law and softening are not consulted:
+ * set them as well (nbx_ctx_set_law, nbx_ctx_set_softening) for nbx_ctx_energy or an all-pairs check of the same system. */
+int nbx_leaf_plan_set_softening(nbx_leaf_plan* plan, double epsilon);
+int nbx_leaf_plan_get_softening(const nbx_leaf_plan* plan, double* epsilon);
 
 /* ---- the octree built on the device ---------------------------------------------------------------
  * A fixed-depth octree (quadtree in 2D) over the bodies RESIDENT in a single-shard context, with the near and far lists of a

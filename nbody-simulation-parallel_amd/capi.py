@@ -56,6 +56,8 @@ ABI = [
     ("nbx_leaf_plan_set_far_order", _i, [_vp, _i]),
     ("nbx_leaf_plan_get_far_order", _i, [_vp, _pi]),
     ("nbx_leaf_plan_get_cell_quadrupoles", _i, [_vp, _vp]),
+    ("nbx_leaf_plan_set_softening", _i, [_vp, _d]),
+    ("nbx_leaf_plan_get_softening", _i, [_vp, _pd]),
     ("nbx_leaf_plan_create_octree", _i, [_c.POINTER(_vp), _vp, _i, _d]),
     ("nbx_leaf_plan_create_octree_adaptive", _i, [_c.POINTER(_vp), _vp, _i, _i, _d]),
     ("nbx_leaf_plan_rebuild_octree", _i, [_vp, _vp]),
@@ -264,7 +266,7 @@ def leapfrog_hip_n_body(bodies: np.ndarray, dt: float, nsteps: int, G: float = R
     return ms.value
 
 
-LAW_BRUTE, LAW_TREE_LEAF, LAW_FMM_P2P = 0, 1, 2
+LAW_BRUTE, LAW_TREE_LEAF, LAW_FMM_P2P, LAW_NEWTON = 0, 1, 2, 3   # LAW_NEWTON: plans only, needs LeafPlan.set_softening > 0
 FAR_MONOPOLE, FAR_QUADRUPOLE = 0, 1
 FORCE_LAW_REFERENCE, FORCE_LAW_NEWTON = 0, 1
 
@@ -445,6 +447,17 @@ class LeafPlan:
     def far_order(self) -> int:
         v = ctypes.c_int(-1)
         self._ck(self.lib.nbx_leaf_plan_get_far_order(self.h, ctypes.byref(v)), "nbx_leaf_plan_get_far_order")
+        return v.value
+
+    def set_softening(self, epsilon: float):
+        """The softening length of LAW_NEWTON, m_j d / (r^2 + epsilon^2)^(3/2) (nbx_leaf_plan_set_softening): 0 (every plan's start)
+        or in [1e-6, 1e15].  It is the plan's: it survives set_cells and octree rebuilds; the other laws never read it."""
+        self._ck(self.lib.nbx_leaf_plan_set_softening(self.h, float(epsilon)), "nbx_leaf_plan_set_softening")
+
+    @property
+    def softening(self) -> float:
+        v = ctypes.c_double(-1.0)
+        self._ck(self.lib.nbx_leaf_plan_get_softening(self.h, ctypes.byref(v)), "nbx_leaf_plan_get_softening")
         return v.value
 
     def get_cell_quadrupoles(self) -> np.ndarray:

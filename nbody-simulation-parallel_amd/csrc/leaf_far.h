@@ -104,6 +104,8 @@ struct FarDevice {
     double* leaf_quad = nullptr;           // [n_leaves][6]: central second moments of a leaf about its OWN centre of mass (3D order; 2D uses xx, yy, xy)
     double* cell_quad = nullptr;           // [n_cells][dim (dim + 1) / 2] fp64 Q as the far pass used them, before the division by M and the fp32 rounding
     float4* cell_qrec = nullptr;           // [n_cells][quad_rec_vecs(dim)] fp32 q = Q / M and its trace, next to cell_rec
+    // ---- NBX_LAW_NEWTON only: the plan's softening length squared, set per far pass (no other law reads it) ----
+    float eps2 = 0.0f;
 };
 
 // The fp32 record of a cell's second moments, q = Q / M (all zeros: the cell attracts as its monopole alone):

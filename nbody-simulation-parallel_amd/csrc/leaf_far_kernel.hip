@@ -35,6 +35,11 @@
 //  the law skips or softens the pair it is 0 and the term is the monopole's, bit for bit.  The q records ride in a second LDS tile
 //  (32 B per record in 3D, 16 B in 2D) in the same two layouts; everything else -- one wave per FarBlock, float2 arithmetic on two
 //  records, the fp64 flush, the lane groups meeting in LDS in group order, one writer per slot -- is the monopole pass's.
+//  Under NBX_LAW_NEWTON (m_j d / rho^3, rho^2 = r^2 + eps^2; leaf_law.h) the pseudo-body is a body like any other, and the second-order
+//  term of sum m_j (R + s_j) / (|R + s_j|^2 + eps^2)^(3/2) is, exactly,
+//      (M / rho^3) [ R (1 - (3/2) tr(q) / rho^2 + (15/2) R^T q R / rho^4) - 3 q R / rho^2 ]
+//  -- the same expression with the coefficients (2, 12, 4) replaced by (3/2, 15/2, 3) and rho^2 in every denominator, u = R / rho^2
+//  included; leaf_weight_ri hands back 1 / rho^2.
 #include "leaf_far.h"
 #include "leaf_law.h"
 
@@ -248,6 +253,7 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
     const float ix = xf[0], iy = xf[2], iz = (D == 3) ? xf[4] : 0.0f;
     const f2 ix2 = {ix, ix}, iy2 = {iy, iy}, iz2 = {iz, iz};
     const float4 pad_rec = make_float4(kFar, kFar, (D == 3) ? kFar : 0.0f, 0.0f);
+    const float eps2 = LAW == NBX_LAW_NEWTON ? d.eps2 : 0.0f;
     f2 ax = {0.f, 0.f}, ay = {0.f, 0.f}, az = {0.f, 0.f};
     double sx = 0.0, sy = 0.0, sz = 0.0;
     unsigned pending = 0;                                         // wave-uniform
@@ -300,7 +306,7 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
         r2 = __builtin_elementwise_fma(dy, dy, r2);
         if (D == 3) r2 = __builtin_elementwise_fma(dz, dz, r2);
         float ria, rib;
-        const f2 w = {leaf_weight_ri<D, LAW>(r2.x, sm2.x, dx.x, dy.x, dz.x, ria), leaf_weight_ri<D, LAW>(r2.y, sm2.y, dx.y, dy.y, dz.y, rib)};
+        const f2 w = {leaf_weight_ri<D, LAW>(r2.x, sm2.x, dx.x, dy.x, dz.x, ria, eps2), leaf_weight_ri<D, LAW>(r2.y, sm2.y, dx.y, dy.y, dz.y, rib, eps2)};
         const f2 ri = {ria, rib};
         const f2 ux = dx * ri, uy = dy * ri;
         f2 gx = qxx * ux, gy = qxy * ux, gz = {0.f, 0.f};        // g = q u
@@ -318,7 +324,9 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
         f2 uqu = ux * gx;
         uqu = __builtin_elementwise_fma(uy, gy, uqu);
         if (D == 3) uqu = __builtin_elementwise_fma(uz, gz, uqu);
-        const f2 one = {1.f, 1.f}, twelve = {12.f, 12.f}, m2 = {-2.f, -2.f}, m4 = {-4.f, -4.f};
+        // the term's three coefficients: of tr(q) / r^2, of u^T q u and of q u (d / r^4: 2, 12, 4; softened Newton: 3/2, 15/2, 3)
+        constexpr float kTr = LAW == NBX_LAW_NEWTON ? 1.5f : 2.f, kUqu = LAW == NBX_LAW_NEWTON ? 7.5f : 12.f, kQu = LAW == NBX_LAW_NEWTON ? 3.f : 4.f;
+        const f2 one = {1.f, 1.f}, twelve = {kUqu, kUqu}, m2 = {-kTr, -kTr}, m4 = {-kQu, -kQu};
         f2 sc = __builtin_elementwise_fma(m2 * qtr, ri, one);
         sc = __builtin_elementwise_fma(twelve, uqu, sc);
         const f2 vx = __builtin_elementwise_fma(sc, dx, m4 * gx), vy = __builtin_elementwise_fma(sc, dy, m4 * gy);
@@ -337,7 +345,7 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
         f2 r2 = dx * dx;
         r2 = __builtin_elementwise_fma(dy, dy, r2);
         if (D == 3) r2 = __builtin_elementwise_fma(dz, dz, r2);
-        const f2 w = {leaf_weight<D, LAW>(r2.x, sm2.x, dx.x, dy.x, dz.x), leaf_weight<D, LAW>(r2.y, sm2.y, dx.y, dy.y, dz.y)};
+        const f2 w = {leaf_weight<D, LAW>(r2.x, sm2.x, dx.x, dy.x, dz.x, eps2), leaf_weight<D, LAW>(r2.y, sm2.y, dx.y, dy.y, dz.y, eps2)};
         ax = __builtin_elementwise_fma(w, dx, ax);
         ay = __builtin_elementwise_fma(w, dy, ay);
         if (D == 3) az = __builtin_elementwise_fma(w, dz, az);
@@ -443,11 +451,11 @@ __global__ __launch_bounds__(64) void far_kernel(FarDevice d) {
 
 typedef void (*FarKernel)(FarDevice);
 FarKernel pick_far(int dim, int law, int order) {
-    static const FarKernel table[2][2][3] = {
-        {{far_kernel<2, NBX_LAW_BRUTE, 0>, far_kernel<2, NBX_LAW_TREE_LEAF, 0>, far_kernel<2, NBX_LAW_FMM_P2P, 0>},
-         {far_kernel<3, NBX_LAW_BRUTE, 0>, far_kernel<3, NBX_LAW_TREE_LEAF, 0>, far_kernel<3, NBX_LAW_FMM_P2P, 0>}},
-        {{far_kernel<2, NBX_LAW_BRUTE, 1>, far_kernel<2, NBX_LAW_TREE_LEAF, 1>, far_kernel<2, NBX_LAW_FMM_P2P, 1>},
-         {far_kernel<3, NBX_LAW_BRUTE, 1>, far_kernel<3, NBX_LAW_TREE_LEAF, 1>, far_kernel<3, NBX_LAW_FMM_P2P, 1>}}};
+    static const FarKernel table[2][2][4] = {
+        {{far_kernel<2, NBX_LAW_BRUTE, 0>, far_kernel<2, NBX_LAW_TREE_LEAF, 0>, far_kernel<2, NBX_LAW_FMM_P2P, 0>, far_kernel<2, NBX_LAW_NEWTON, 0>},
+         {far_kernel<3, NBX_LAW_BRUTE, 0>, far_kernel<3, NBX_LAW_TREE_LEAF, 0>, far_kernel<3, NBX_LAW_FMM_P2P, 0>, far_kernel<3, NBX_LAW_NEWTON, 0>}},
+        {{far_kernel<2, NBX_LAW_BRUTE, 1>, far_kernel<2, NBX_LAW_TREE_LEAF, 1>, far_kernel<2, NBX_LAW_FMM_P2P, 1>, far_kernel<2, NBX_LAW_NEWTON, 1>},
+         {far_kernel<3, NBX_LAW_BRUTE, 1>, far_kernel<3, NBX_LAW_TREE_LEAF, 1>, far_kernel<3, NBX_LAW_FMM_P2P, 1>, far_kernel<3, NBX_LAW_NEWTON, 1>}}};
     return table[order][dim - 2][law];
 }
 

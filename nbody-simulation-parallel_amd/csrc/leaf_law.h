@@ -20,9 +20,16 @@ static_assert(kTreeSkipF < 9.0e-7f, "a target outside the close set (nbx_interna
 // Weight of d = p_j - p_i in the law's sum for ONE pair, every special case included: m_j / r^4 for an ordinary pair.  `ri` receives
 // the reciprocal the weight was made of, 1 / r^2, for the far field's second-order term (leaf_far_kernel.hip) -- or 0 where the law
 // skips or softens the pair: the correction of that pair is then dropped (every factor of it carries ri).
+// NBX_LAW_NEWTON (the only law that reads eps2 = epsilon^2 > 0): rho^2 = r^2 + eps2, weight m_j / rho^3, ri = 1 / rho^2; no special
+// case exists -- d = 0 gives a finite weight times a zero vector.  rs m and rs rs are formed first: neither leaves fp32's range while
+// m / eps^3 stays inside it (the plan checks that before it launches), and a massless pad at 1e18 gives 0 x 3e-37 = 0, never a NaN.
 template <int D, int LAW>
-__device__ __forceinline__ float leaf_weight_ri(float r2, float mj, float dx, float dy, float dz, float& ri) {
-    if (LAW == NBX_LAW_BRUTE) {
+__device__ __forceinline__ float leaf_weight_ri(float r2, float mj, float dx, float dy, float dz, float& ri, float eps2 = 0.0f) {
+    if (LAW == NBX_LAW_NEWTON) {
+        const float rs = __builtin_amdgcn_rsqf(r2 + eps2);
+        ri = rs * rs;
+        return ri * (rs * mj);
+    } else if (LAW == NBX_LAW_BRUTE) {
         const float g = (r2 < nbx::kR2SkipF) ? __builtin_inff() : r2;           // methods.cpp:24
         ri = __builtin_amdgcn_rcpf(g);
         return mj * ri * ri;
@@ -46,9 +53,9 @@ __device__ __forceinline__ float leaf_weight_ri(float r2, float mj, float dx, fl
 }
 
 template <int D, int LAW>
-__device__ __forceinline__ float leaf_weight(float r2, float mj, float dx, float dy, float dz) {
+__device__ __forceinline__ float leaf_weight(float r2, float mj, float dx, float dy, float dz, float eps2 = 0.0f) {
     float ri;
-    return leaf_weight_ri<D, LAW>(r2, mj, dx, dy, dz, ri);
+    return leaf_weight_ri<D, LAW>(r2, mj, dx, dy, dz, ri, eps2);
 }
 #endif
 

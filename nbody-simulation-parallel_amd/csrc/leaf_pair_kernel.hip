@@ -30,7 +30,10 @@
 //    loop with no compare at all: r^2 biased by 2^-47, an identical position contributes m 2^94 x 0 = 0 as every law
 //    asks.  Each wave decides for itself from its lanes' own coordinates (and the call's largest mass); the other waves
 //    take the guarded loop (the smallest r^2 of a trip's four pairs, one compare, a wave vote, and the law's exact
-//    weights for the wave that saw a pair below the threshold).
+//    weights for the wave that saw a pair below the threshold);
+//  * NBX_LAW_NEWTON (extension: m_j d / (r^2 + eps^2)^(3/2), eps the plan's softening length) is the simplest law here: with eps^2 in
+//    place of the 2^-47 bias no special case exists, so EVERY wave runs the unguarded loop -- no close-set test, no mass bound, no
+//    vote -- with v_rsq_f32 where the other laws have v_rcp_f32 (PairTerm::plain).
 // fp32 sums over at most 256 terms per lane, flushed into fp64 accumulators.  No atomics, a fixed summation order,
 // every output written once.  Leaves are small (the reference caps them at 100 bodies, methods.h:26), so the launch
 // is tens of thousands of short workgroups; HBM traffic is 16 B per (workgroup, source body), served mostly from L2.
@@ -76,6 +79,7 @@ struct LeafArgs {
     const LeafBlock* __restrict__ blocks;
     double* __restrict__ acc;          // [dim][pslots]
     const uint32_t* __restrict__ max_mass_bits;   // bit pattern of the largest |mass| as fp32 (leaf_gather_kernel); a NaN compares above every number
+    float eps2;                        // NBX_LAW_NEWTON: the plan's softening length squared (> 0); no other law reads it
 };
 
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -99,7 +103,23 @@ struct PairTerm {
         r2 = __builtin_elementwise_fma(dy, dy, r2);
         if (D == 3) r2 = __builtin_elementwise_fma(dz, dz, r2);
     }
+    template <int LAW, bool PACKED = false>
     __device__ __forceinline__ f2 plain() const {
+        if (LAW == NBX_LAW_NEWTON) {
+            // r2 carries eps^2 as its bias: m / (r^2 + eps^2)^(3/2) = rs^3 m, 2 v_rsq_f32 + 3 v_pk_mul per two pairs.  Nothing overflows
+            // while m / eps^3 is finite (plan_check_law), and a massless pad at 1e18 gives 2e-55 -> 0, times 0: exact zeros, never a NaN.
+            // The order of the three products is chosen per kernel by the registers the allocator then needs (every instantiation at
+            // or below its TREE_LEAF twin, profiles/r12/newton_tree.txt): ((m rs) rs) rs in the one-leaf workgroups, ((rs rs) rs) m in
+            // the packed waves -- the other way round, and either mixed order, costs 2 and 8 VGPRs.  The packed order forms rho^-3
+            // BEFORE the mass: it is a normal fp32 number only for rho = sqrt(r^2 + eps^2) < 4.4e12 and loses bits beyond (the one-leaf
+            // order and leaf_weight_ri do not).  That is the law's documented range (include/nbody_hip.h); the other laws' 1 / r^4
+            // leaves fp32's normal range at r = 3e9 already.
+            const f2 rs = {__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
+            if (PACKED) return ((rs * rs) * rs) * sm;
+            f2 t = rs * sm;
+            t = t * rs;
+            return t * rs;
+        }
         f2 w = {__builtin_amdgcn_rcpf(r2.x), __builtin_amdgcn_rcpf(r2.y)};
         w = w * w;
         return w * sm;
@@ -157,8 +177,9 @@ struct Sums {
 // without it a trip is 26 VALU (6 v_pk_add, 6 + 6 v_pk_fma, 4 v_pk_mul, 4 v_rcp_f32) and half an address increment, and the
 // LDS reads of the trip after next are in flight while a trip is computed.
 template <int D, int LAW, bool GUARD>
-__device__ __forceinline__ void consume(const float4* __restrict__ s, const unsigned T, const f2 ix2, const f2 iy2, const f2 iz2, Sums<D>& S) {
-    const f2 bias = GUARD ? f2{0.f, 0.f} : f2{kTiny, kTiny};
+__device__ __forceinline__ void consume(const float4* __restrict__ s, const unsigned T, const f2 ix2, const f2 iy2, const f2 iz2, Sums<D>& S, const float eps2) {
+    static_assert(!(GUARD && LAW == NBX_LAW_NEWTON), "the softened law has no special case: every wave runs the unguarded form");
+    const f2 bias = LAW == NBX_LAW_NEWTON ? f2{eps2, eps2} : GUARD ? f2{0.f, 0.f} : f2{kTiny, kTiny};
     const unsigned ndt = T >> 1;
     unsigned done = 0;
     while (done < ndt) {                                    // wave-uniform bookkeeping
@@ -169,7 +190,7 @@ __device__ __forceinline__ void consume(const float4* __restrict__ s, const unsi
             // the trip after next is read while this one is computed: two register sets, taking turns (no copies)
             auto trip = [&](const float4 A0, const float4 B0, const float4 A1, const float4 B1) {
                 const PairTerm<D> q0(A0, B0, ix2, iy2, iz2, bias), q1(A1, B1, ix2, iy2, iz2, bias);
-                const f2 w0 = q0.plain(), w1 = q1.plain();
+                const f2 w0 = q0.template plain<LAW>(), w1 = q1.template plain<LAW>();
                 S.add(q0, w0);
                 S.add(q1, w1);
             };
@@ -195,8 +216,8 @@ __device__ __forceinline__ void consume(const float4* __restrict__ s, const unsi
                     w0 = q0.template guarded<LAW>();
                     w1 = q1.template guarded<LAW>();
                 } else {
-                    w0 = q0.plain();
-                    w1 = q1.plain();
+                    w0 = q0.template plain<LAW>();
+                    w1 = q1.template plain<LAW>();
                 }
                 S.add(q0, w0);
                 S.add(q1, w1);
@@ -206,7 +227,7 @@ __device__ __forceinline__ void consume(const float4* __restrict__ s, const unsi
         done += n;
     }
     const PairTerm<D> q0(s[0], s[1], ix2, iy2, iz2, bias);
-    const f2 w0 = (GUARD && __builtin_expect(q0.template special<LAW>() != 0ull, 0)) ? q0.template guarded<LAW>() : q0.plain();
+    const f2 w0 = (GUARD && __builtin_expect(q0.template special<LAW>() != 0ull, 0)) ? q0.template guarded<LAW>() : q0.template plain<LAW>();
     S.add(q0, w0);
     S.pending += 2u;
 }
@@ -316,8 +337,9 @@ __device__ __forceinline__ void leaf_pair_body(const LeafArgs& a, const unsigned
                 const unsigned pairs = cur >> 1;
                 const unsigned T = (((pairs + P - 1u) * inv_P) >> 16) | 1u;
                 const float4* s = tile + 2u * g * T;
-                if (safe) consume<D, LAW, false>(s, T, ix2, iy2, iz2, S);
-                else consume<D, LAW, true>(s, T, ix2, iy2, iz2, S);
+                if constexpr (LAW == NBX_LAW_NEWTON) consume<D, LAW, false>(s, T, ix2, iy2, iz2, S, a.eps2);   // no close set, no mass bound, no vote
+                else if (safe) consume<D, LAW, false>(s, T, ix2, iy2, iz2, S, 0.0f);
+                else consume<D, LAW, true>(s, T, ix2, iy2, iz2, S, 0.0f);
             }
         }
     }
@@ -360,6 +382,7 @@ struct LeafPackArgs {
     const PackSub* __restrict__ subs;
     double* __restrict__ acc;
     const uint32_t* __restrict__ max_mass_bits;
+    float eps2;                        // as LeafArgs::eps2
 };
 
 #ifndef NBX_PACK_WAVES
@@ -411,7 +434,8 @@ __device__ __forceinline__ void leaf_pack_body(const LeafPackArgs& a, const unsi
     // lanes of an unused leaf slot hold no target: they must not drag the wave into the guarded loop
     auto close = [](const float x, const float y, const float z) { return !(__builtin_fabsf(x) >= kCloseCoord && __builtin_fabsf(y) >= kCloseCoord && (D == 2 || __builtin_fabsf(z) >= kCloseCoord)); };
     const bool in_close_set = my.count != 0u && (close(ix, iy, iz) || close(jx, jy, jz));
-    const bool safe = __builtin_amdgcn_ballot_w64(in_close_set) == 0ull && *a.max_mass_bits <= __builtin_bit_cast(uint32_t, (float)kFastMaxMass);
+    // the softened law has no special case: every wave runs the unguarded form, whatever its targets and the masses
+    const bool safe = LAW == NBX_LAW_NEWTON || (__builtin_amdgcn_ballot_w64(in_close_set) == 0ull && *a.max_mass_bits <= __builtin_bit_cast(uint32_t, (float)kFastMaxMass));
     // this leaf's copy runs, as {end of the run in the stream, byte offset of the run's first unit minus 16 x its stream position}
     // (32-bit byte offsets from a scalar base: the plan packs nothing beyond 2^28 units), and behind the last one the PAD RUN:
     // it never ends, and every position of it is the launch's pad pair (its positions are masked to zero)
@@ -448,13 +472,13 @@ __device__ __forceinline__ void leaf_pack_body(const LeafPackArgs& a, const unsi
     static_assert(kPackPairsPerTrip == 2, "the loops below");
     // one form of the pair term per wave (GUARD: a special case of the law is possible for one of this wave's targets)
     auto compute_with = [&](auto guard, const float4 (&A)[2], const float4 (&B)[2]) {
-        constexpr bool GUARD = decltype(guard)::value;
-        const f2 bias = GUARD ? f2{0.f, 0.f} : f2{kTiny, kTiny};
+        constexpr bool GUARD = decltype(guard)::value && LAW != NBX_LAW_NEWTON;
+        const f2 bias = LAW == NBX_LAW_NEWTON ? f2{a.eps2, a.eps2} : GUARD ? f2{0.f, 0.f} : f2{kTiny, kTiny};
         auto term = [&](const float4 A1, const float4 B1, const f2 x2, const f2 y2, const f2 z2, Sums<D>& S) {
             const PairTerm<D> q(A1, B1, x2, y2, z2, bias);
             f2 wgt;
             if (GUARD && __builtin_expect(q.template special<LAW>() != 0ull, 0)) wgt = q.template guarded<LAW>();
-            else wgt = q.plain();
+            else wgt = q.template plain<LAW, true>();
             S.add(q, wgt);
         };
         if (S0.pending + 4u > kFlushTerms) {
@@ -720,27 +744,27 @@ __global__ __launch_bounds__(256) void leaf_forces_by_body_kernel(const double* 
 
 typedef void (*LeafKernel)(LeafArgs);
 LeafKernel pick(int dim, int law, int waves) {
-    static const LeafKernel table[2][2][3] = {
-        {{leaf_pair_kernel<2, NBX_LAW_BRUTE, 1>, leaf_pair_kernel<2, NBX_LAW_TREE_LEAF, 1>, leaf_pair_kernel<2, NBX_LAW_FMM_P2P, 1>},
-         {leaf_pair_kernel<3, NBX_LAW_BRUTE, 1>, leaf_pair_kernel<3, NBX_LAW_TREE_LEAF, 1>, leaf_pair_kernel<3, NBX_LAW_FMM_P2P, 1>}},
-        {{leaf_pair_kernel<2, NBX_LAW_BRUTE, 2>, leaf_pair_kernel<2, NBX_LAW_TREE_LEAF, 2>, leaf_pair_kernel<2, NBX_LAW_FMM_P2P, 2>},
-         {leaf_pair_kernel<3, NBX_LAW_BRUTE, 2>, leaf_pair_kernel<3, NBX_LAW_TREE_LEAF, 2>, leaf_pair_kernel<3, NBX_LAW_FMM_P2P, 2>}}};
+    static const LeafKernel table[2][2][4] = {
+        {{leaf_pair_kernel<2, NBX_LAW_BRUTE, 1>, leaf_pair_kernel<2, NBX_LAW_TREE_LEAF, 1>, leaf_pair_kernel<2, NBX_LAW_FMM_P2P, 1>, leaf_pair_kernel<2, NBX_LAW_NEWTON, 1>},
+         {leaf_pair_kernel<3, NBX_LAW_BRUTE, 1>, leaf_pair_kernel<3, NBX_LAW_TREE_LEAF, 1>, leaf_pair_kernel<3, NBX_LAW_FMM_P2P, 1>, leaf_pair_kernel<3, NBX_LAW_NEWTON, 1>}},
+        {{leaf_pair_kernel<2, NBX_LAW_BRUTE, 2>, leaf_pair_kernel<2, NBX_LAW_TREE_LEAF, 2>, leaf_pair_kernel<2, NBX_LAW_FMM_P2P, 2>, leaf_pair_kernel<2, NBX_LAW_NEWTON, 2>},
+         {leaf_pair_kernel<3, NBX_LAW_BRUTE, 2>, leaf_pair_kernel<3, NBX_LAW_TREE_LEAF, 2>, leaf_pair_kernel<3, NBX_LAW_FMM_P2P, 2>, leaf_pair_kernel<3, NBX_LAW_NEWTON, 2>}}};
     return table[waves - 1][dim - 2][law];
 }
 
 typedef void (*PackKernel)(LeafPackArgs);
 PackKernel pick_pack(int dim, int law) {
-    static const PackKernel table[2][3] = {
-        {leaf_pack_kernel<2, NBX_LAW_BRUTE>, leaf_pack_kernel<2, NBX_LAW_TREE_LEAF>, leaf_pack_kernel<2, NBX_LAW_FMM_P2P>},
-        {leaf_pack_kernel<3, NBX_LAW_BRUTE>, leaf_pack_kernel<3, NBX_LAW_TREE_LEAF>, leaf_pack_kernel<3, NBX_LAW_FMM_P2P>}};
+    static const PackKernel table[2][4] = {
+        {leaf_pack_kernel<2, NBX_LAW_BRUTE>, leaf_pack_kernel<2, NBX_LAW_TREE_LEAF>, leaf_pack_kernel<2, NBX_LAW_FMM_P2P>, leaf_pack_kernel<2, NBX_LAW_NEWTON>},
+        {leaf_pack_kernel<3, NBX_LAW_BRUTE>, leaf_pack_kernel<3, NBX_LAW_TREE_LEAF>, leaf_pack_kernel<3, NBX_LAW_FMM_P2P>, leaf_pack_kernel<3, NBX_LAW_NEWTON>}};
     return table[dim - 2][law];
 }
 
 typedef void (*FusedKernel)(LeafArgs, LeafPackArgs, uint32_t);
 FusedKernel pick_fused(int dim, int law) {
-    static const FusedKernel table[2][3] = {
-        {leaf_fused_kernel<2, NBX_LAW_BRUTE>, leaf_fused_kernel<2, NBX_LAW_TREE_LEAF>, leaf_fused_kernel<2, NBX_LAW_FMM_P2P>},
-        {leaf_fused_kernel<3, NBX_LAW_BRUTE>, leaf_fused_kernel<3, NBX_LAW_TREE_LEAF>, leaf_fused_kernel<3, NBX_LAW_FMM_P2P>}};
+    static const FusedKernel table[2][4] = {
+        {leaf_fused_kernel<2, NBX_LAW_BRUTE>, leaf_fused_kernel<2, NBX_LAW_TREE_LEAF>, leaf_fused_kernel<2, NBX_LAW_FMM_P2P>, leaf_fused_kernel<2, NBX_LAW_NEWTON>},
+        {leaf_fused_kernel<3, NBX_LAW_BRUTE>, leaf_fused_kernel<3, NBX_LAW_TREE_LEAF>, leaf_fused_kernel<3, NBX_LAW_FMM_P2P>, leaf_fused_kernel<3, NBX_LAW_NEWTON>}};
     return table[dim - 2][law];
 }
 
@@ -893,6 +917,8 @@ struct nbx_leaf_plan {
     bool cells_timed = false;       // ... and it recorded the four events
     // ---- the far field's order (nbx_leaf_plan_set_far_order): the plan's own, it outlives cells and rebuilds ----
     int far_order = NBX_FAR_MONOPOLE;
+    // ---- NBX_LAW_NEWTON's softening length (nbx_leaf_plan_set_softening): the plan's own like the order; no other law reads it ----
+    double softening = 0.0;
     bool quads_evaluated = false;   // the last evaluation with these cells ran at order 1: cell_quad holds its second moments
     char* quad_arena = nullptr;     // leaf_quad, cell_quad, cell_qrec of the cells as they stand; never allocated at order 0
     size_t quad_arena_bytes = 0;
@@ -1004,7 +1030,7 @@ extern "C" int nbx_leaf_pair_forces(const void* bodies, size_t n, int dim, size_
                                     float* kernel_ms) {
     if (kernel_ms) *kernel_ms = 0.0f;
     if (dim != 2 && dim != 3) return fail(NBX_ERR_INVALID, "dim must be 2 or 3");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "unknown law");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, law == NBX_LAW_NEWTON ? "NBX_LAW_NEWTON needs a plan (nbx_leaf_plan_set_softening): the one-shot call has no softening length" : "unknown law");
     if ((!bodies || !forces_out) && n) return fail(NBX_ERR_INVALID, "null argument");
     const size_t min_stride = (size_t)(2 * dim + 1) * sizeof(double);
     if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
@@ -1106,7 +1132,7 @@ extern "C" int nbx_leaf_pair_forces(const void* bodies, size_t n, int dim, size_
                        reinterpret_cast<float*>(xp), d_max_mass);
     NBX_HIP_TRY(hipGetLastError());
     LeafArgs a;
-    a.xp = xp; a.pslots = (uint32_t)pslots; a.ops = d_ops; a.blocks = d_blocks; a.acc = acc; a.max_mass_bits = d_max_mass;
+    a.xp = xp; a.pslots = (uint32_t)pslots; a.ops = d_ops; a.blocks = d_blocks; a.acc = acc; a.max_mass_bits = d_max_mass; a.eps2 = 0.0f;
     NBX_HIP_TRY(hipEventRecord(d.ev0, d.stream));
     if (!blocks.empty()) {   // one-leaf workgroups first: they are the long ones
         hipLaunchKernelGGL(pick(dim, law, waves), dim3((unsigned)blocks.size()), dim3(64u * (unsigned)waves), 0, d.stream, a);
@@ -1114,7 +1140,7 @@ extern "C" int nbx_leaf_pair_forces(const void* bodies, size_t n, int dim, size_
     }
     if (!plan.pack_blocks.empty()) {
         LeafPackArgs pa;
-        pa.xp = xp; pa.pslots = (uint32_t)pslots; pa.ops = d_ops; pa.blocks = d_packs; pa.subs = d_subs; pa.acc = acc; pa.max_mass_bits = d_max_mass;
+        pa.xp = xp; pa.pslots = (uint32_t)pslots; pa.ops = d_ops; pa.blocks = d_packs; pa.subs = d_subs; pa.acc = acc; pa.max_mass_bits = d_max_mass; pa.eps2 = 0.0f;
         hipLaunchKernelGGL(pick_pack(dim, law), dim3((unsigned)plan.pack_blocks.size()), dim3(64), 0, d.stream, pa);
         NBX_HIP_TRY(hipGetLastError());
     }
@@ -1149,14 +1175,32 @@ int plan_mark_done(nbx_leaf_plan* p, hipStream_t s) {
     return NBX_OK;
 }
 
+float plan_eps2(const nbx_leaf_plan* p) { return (float)(p->softening * p->softening); }
+
+// What an evaluation under `law` needs beyond its arguments, before anything is launched.  Only NBX_LAW_NEWTON needs anything: a
+// softening length, and masses for which the heaviest body's weight at zero distance, max|m| / eps^3, is a finite, normal fp32 number
+// (the context's rule, nbx_api.hip: neither an overflow nor an all-zero field with status OK).  mass_max < 0: not known, not checked.
+int plan_check_law(const nbx_leaf_plan* p, int law, double mass_max) {
+    if (law != NBX_LAW_NEWTON) return NBX_OK;
+    if (!(p->softening > 0.0)) return fail(NBX_ERR_STATE, "NBX_LAW_NEWTON needs a softening length (nbx_leaf_plan_set_softening)");
+    const double eps3 = (double)plan_eps2(p) * p->softening;
+    if (mass_max >= 0.0 || mass_max != mass_max) {
+        if (!(mass_max / eps3 < 1.0e38)) return fail(NBX_ERR_INVALID, "softening too small for these masses: m / eps^3 must stay finite in fp32");
+        if (mass_max > 0.0 && !(mass_max / eps3 > 1.0e-30)) return fail(NBX_ERR_INVALID, "softening too large for these masses: m / eps^3 underflows in fp32");
+    }
+    return NBX_OK;
+}
+
 // the near field: the pair kernels, which WRITE the slot-ordered sums
 int plan_launch_near(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
     if (p->n_blocks == 0 && p->n_packs == 0) return NBX_OK;
     if (timed) NBX_HIP_TRY(hipEventRecord(p->ev0, s));
     LeafArgs a;
     a.xp = p->xp; a.pslots = (uint32_t)p->pslots; a.ops = p->ops; a.blocks = p->blocks; a.acc = p->sums; a.max_mass_bits = p->max_mass;
+    a.eps2 = plan_eps2(p);
     LeafPackArgs pa;
     pa.xp = p->xp; pa.pslots = (uint32_t)p->pslots; pa.ops = p->ops; pa.blocks = p->packs; pa.subs = p->subs; pa.acc = p->sums; pa.max_mass_bits = p->max_mass;
+    pa.eps2 = a.eps2;
     if (p->n_blocks && p->n_packs && p->waves == 1) {   // both kinds (packing implies one-wave workgroups): one launch, the one-leaf workgroups first
         hipLaunchKernelGGL(pick_fused(p->dim, law), dim3((unsigned)(p->n_blocks + p->n_packs)), dim3(64), 0, s, a, pa, (uint32_t)p->n_blocks);
         NBX_HIP_TRY(hipGetLastError());
@@ -1206,6 +1250,7 @@ int plan_fit_quads(nbx_leaf_plan* p) {
 int plan_launch_far(nbx_leaf_plan* p, int law, hipStream_t s, bool timed, bool with_moments = true) {
     if (!p->far.n_cells) return NBX_OK;
     nbx_far::FarDevice f = p->far;
+    f.eps2 = plan_eps2(p);
     if (!with_moments && !p->quads_evaluated) f.order = NBX_FAR_MONOPOLE;   // no second moments of these positions: the order the sums were made at
     if (timed) NBX_HIP_TRY(hipEventRecord(p->evf0, s));
     NBX_HIP_TRY(nbx_far::enqueue_far(f, p->dim, law, s));
@@ -1628,12 +1673,23 @@ int nbx_leaf_plan_info(const nbx_leaf_plan* p, size_t* slots, size_t* runs, size
 int nbx_leaf_plan_forces(nbx_leaf_plan* p, const void* bodies, size_t stride_bytes, int law, double G, double* forces_out, float* kernel_ms) {
     if (kernel_ms) *kernel_ms = 0.0f;
     if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "unknown law");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if ((!bodies || !forces_out) && p->n) return fail(NBX_ERR_INVALID, "null argument");
     const size_t min_stride = (size_t)(2 * p->dim + 1) * sizeof(double);
     if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
         return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
     if (int src = plan_needs_structure(p)) return src;
+    if (law == NBX_LAW_NEWTON) {   // one host pass over the masses about to be copied (no other law pays for it)
+        double mass_max = 0.0;
+        const char* const m0 = static_cast<const char*>(bodies) + 2 * (size_t)p->dim * sizeof(double);
+        for (size_t i = 0; i < p->n; ++i) {
+            double m;
+            std::memcpy(&m, m0 + i * stride_bytes, sizeof m);
+            m = std::fabs(m);
+            if (!(m <= mass_max)) mass_max = m;      // a NaN stays: refused below
+        }
+        if (int lrc = plan_check_law(p, law, mass_max)) return lrc;
+    }
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
@@ -1678,11 +1734,12 @@ static int plan_gather_resident(nbx_leaf_plan* p, nbx_ctx* c, hipStream_t s) {
 int nbx_leaf_plan_forces_ctx(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double* forces_out, float* kernel_ms) {
     if (kernel_ms) *kernel_ms = 0.0f;
     if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "unknown law");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
         return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
     if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
     if (int src = plan_needs_structure(p)) return src;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
@@ -1747,13 +1804,14 @@ static int plan_enqueue_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double signe
 
 int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps) {
     if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "unknown law");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if (nsteps < 0) return fail(NBX_ERR_INVALID, "nsteps must be >= 0");
     if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
         return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
     if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
     if (nsteps == 0) return NBX_OK;
     if (int src = plan_needs_structure(p)) return src;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
@@ -1775,11 +1833,12 @@ int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double d
 
 int nbx_leaf_plan_step_octree(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
     if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "unknown law");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if (nsteps < 0 || rebuild_every < 0) return fail(NBX_ERR_INVALID, "nsteps and rebuild_every must be >= 0");
     if (int rc = plan_check_ctx(p, c)) return rc;
     if (rebuild_every > 0 && !p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
     if (nsteps == 0) return NBX_OK;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
@@ -1894,6 +1953,26 @@ int nbx_leaf_plan_get_far_order(const nbx_leaf_plan* p, int* order) {
     return NBX_OK;
 }
 
+int nbx_leaf_plan_set_softening(nbx_leaf_plan* p, double epsilon) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (!(epsilon == 0.0 || (epsilon >= 1.0e-6 && epsilon <= 1.0e15))) return fail(NBX_ERR_INVALID, "softening must be 0 or in [1e-6, 1e15]");
+    DeviceScope scope;
+    int rc = plan_set_device(p);
+    if (rc) return rc;
+    hipStream_t s = p->stream;
+    if ((rc = plan_order_after_last(p, s))) return rc;
+    NBX_HIP_TRY(hipStreamSynchronize(s));               // the last evaluation is over (its launches carry their own copy of eps^2 anyway)
+    p->softening = epsilon;
+    return plan_mark_done(p, s);
+}
+
+int nbx_leaf_plan_get_softening(const nbx_leaf_plan* p, double* epsilon) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (!epsilon) return fail(NBX_ERR_INVALID, "epsilon is null");
+    *epsilon = p->softening;
+    return NBX_OK;
+}
+
 int nbx_leaf_plan_get_cell_quadrupoles(nbx_leaf_plan* p, double* q_out) {
     if (!p) return fail(NBX_ERR_INVALID, "plan is null");
     if (p->far_order != NBX_FAR_QUADRUPOLE) return fail(NBX_ERR_STATE, "the plan's far order is NBX_FAR_MONOPOLE: no second moments are computed");
@@ -1946,14 +2025,21 @@ int nbx_leaf_plan_cell_info(nbx_leaf_plan* p, size_t* n_cells, size_t* far_entri
 int nbx_leaf_plan_time_kernel(nbx_leaf_plan* p, int law, int reps, float* mean_ms) {
     if (!p || !mean_ms) return fail(NBX_ERR_INVALID, "null argument");
     *mean_ms = 0.0f;
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "unknown law");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if (reps < 1 || reps > 1000) return fail(NBX_ERR_INVALID, "reps must be in [1, 1000]");
     if (!p->evaluated) return fail(NBX_ERR_STATE, "evaluate once before timing (the bodies of the last evaluation are used)");
+    if (int lrc = plan_check_law(p, law, -1.0)) return lrc;      // the softening length; the masses below
     DeviceScope scope;
     int rc = plan_set_device(p);
     if (rc) return rc;
     hipStream_t s = p->stream;   // the plan's own stream, behind the last evaluation (see nbx_leaf_plan_get_forces)
     if ((rc = plan_order_after_last(p, s))) return rc;
+    if (law == NBX_LAW_NEWTON) {   // the largest |mass| of the bodies the launches will read: the word the last gather left (fp32 bits)
+        float mass_max = 0.0f;
+        NBX_HIP_TRY(hipMemcpyAsync(&mass_max, p->max_mass, sizeof(float), hipMemcpyDeviceToHost, s));
+        NBX_HIP_TRY(hipStreamSynchronize(s));
+        if (int lrc = plan_check_law(p, law, (double)mass_max)) return lrc;
+    }
     const int timed_from = reps / 2;
     for (int r = 0; r < reps; ++r) {
         if (r == timed_from) NBX_HIP_TRY(hipEventRecord(p->ev0, s));

@@ -115,6 +115,11 @@ void LeafPairSimulationHip<D>::set_far_order(int order) {
     if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::set_far_order", rc);
 }
 template <int D>
+void LeafPairSimulationHip<D>::set_softening(double epsilon) {
+    const int rc = nbx_leaf_plan_set_softening(plan_, epsilon);
+    if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::set_softening", rc);
+}
+template <int D>
 float LeafPairSimulationHip<D>::single_launch_ms(LeafLaw law, double G) {
     float ms = 0.0f;
     const int rc = nbx_leaf_plan_forces_ctx(plan_, ctx_, static_cast<int>(law), G, nullptr, &ms);
@@ -222,6 +227,113 @@ void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double t
     if (rc != NBX_OK) raise_leaf("barnes_hut_hip_adaptive_leaves", rc);
     for (std::size_t l = 0; l < *n_leaves; ++l) *largest_leaf = std::max<std::size_t>(*largest_leaf, offsets[l + 1] - offsets[l]);
 }
+
+// ---- softened Newtonian gravity through the tree ----
+template <int D>
+BarnesHutNewtonHip<D>::BarnesHutNewtonHip(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int depth, int far_order, double G, double epsilon)
+    : n_(bodies.size()), G_(G) {
+    const char* const where = "BarnesHutNewtonHip";
+    if (bodies.empty()) throw std::runtime_error(std::string(where) + ": no bodies");
+    int rc = nbx_ctx_create(&ctx_, leaf_device(), D, bodies.size(), 1, 0);
+    if (!rc) rc = nbx_ctx_upload_bodies(ctx_, bodies.data(), sizeof(Body<D>));
+    if (!rc && leaf_capacity >= 0) rc = nbx_leaf_plan_create_octree_adaptive(&plan_, ctx_, depth, leaf_capacity, theta);
+    else if (!rc) rc = nbx_leaf_plan_create_octree(&plan_, ctx_, depth > 0 ? depth : barnes_hut_hip_depth(bodies.size(), D), theta);
+    if (!rc) rc = nbx_leaf_plan_set_far_order(plan_, far_order);
+    if (!rc) rc = nbx_leaf_plan_set_softening(plan_, epsilon);
+    // the context's own law, for nbx_ctx_energy only: every force of this object is the plan's
+    if (!rc) rc = nbx_ctx_set_softening(ctx_, epsilon);
+    if (!rc) rc = nbx_ctx_set_law(ctx_, NBX_FORCE_LAW_NEWTON);
+    if (rc != NBX_OK) {
+        nbx_leaf_plan_destroy(plan_);
+        nbx_ctx_destroy(ctx_);
+        raise_leaf(where, rc);
+    }
+}
+template <int D>
+BarnesHutNewtonHip<D>::~BarnesHutNewtonHip() {
+    nbx_leaf_plan_destroy(plan_);   // before the context, as in LeafPairSimulationHip
+    nbx_ctx_destroy(ctx_);
+}
+template <int D>
+std::vector<Vector<D>> BarnesHutNewtonHip<D>::forces() {
+    std::vector<Vector<D>> out(n_);
+    const int rc = nbx_leaf_plan_forces_ctx(plan_, ctx_, NBX_LAW_NEWTON, G_, reinterpret_cast<double*>(out.data()), nullptr);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::forces", rc);
+    return out;
+}
+template <int D>
+void BarnesHutNewtonHip<D>::step(double dt, int nsteps, int rebuild_every) {
+    const int rc = nbx_leaf_plan_step_octree(plan_, ctx_, NBX_LAW_NEWTON, G_, dt, nsteps, rebuild_every);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::step", rc);
+}
+template <int D>
+void BarnesHutNewtonHip<D>::energy(double* kinetic, double* potential) {
+    const int rc = nbx_ctx_energy(ctx_, G_, kinetic, potential);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::energy", rc);
+}
+template <int D>
+void BarnesHutNewtonHip<D>::download(std::vector<Body<D>>& bodies) {
+    if (bodies.size() != n_) throw std::runtime_error("BarnesHutNewtonHip::download: body count differs");
+    const int rc = nbx_ctx_download_bodies(ctx_, bodies.data(), sizeof(Body<D>));
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::download", rc);
+}
+template class BarnesHutNewtonHip<2>;
+template class BarnesHutNewtonHip<3>;
+
+template <int D>
+std::vector<Vector<D>> newton_all_pairs_forces_hip(const std::vector<Body<D>>& bodies, double G, double epsilon) {
+    std::vector<Vector<D>> out(bodies.size());
+    if (bodies.empty()) return out;
+    nbx_ctx* ctx = nullptr;
+    int rc = nbx_ctx_create(&ctx, leaf_device(), D, bodies.size(), 1, 0);
+    if (!rc) rc = nbx_ctx_upload_bodies(ctx, bodies.data(), sizeof(Body<D>));
+    if (!rc) rc = nbx_ctx_set_softening(ctx, epsilon);
+    if (!rc) rc = nbx_ctx_set_law(ctx, NBX_FORCE_LAW_NEWTON);
+    if (!rc) rc = nbx_ctx_compute_accel(ctx, NBX_SRC_ALL);
+    if (!rc) rc = nbx_ctx_get_forces(ctx, G, reinterpret_cast<double*>(out.data()));
+    nbx_ctx_destroy(ctx);
+    if (rc != NBX_OK) raise_leaf("newton_all_pairs_forces_hip", rc);
+    return out;
+}
+template std::vector<Vector<2>> newton_all_pairs_forces_hip<2>(const std::vector<Body<2>>&, double, double);
+template std::vector<Vector<3>> newton_all_pairs_forces_hip<3>(const std::vector<Body<3>>&, double, double);
+
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta, int depth, int far_order, double G, double epsilon) {
+    if (bodies.empty()) return {};
+    return BarnesHutNewtonHip<D>(bodies, theta, -1, depth, far_order, G, epsilon).forces();
+}
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, double G, double epsilon) {
+    if (bodies.empty()) return;
+    BarnesHutNewtonHip<D> sim(bodies, theta, -1, depth, far_order, G, epsilon);
+    sim.step(dt, nsteps, rebuild_every);
+    sim.download(bodies);
+}
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, int far_order, double G,
+                                                      double epsilon) {
+    check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_n_body");
+    if (bodies.empty()) return {};
+    return BarnesHutNewtonHip<D>(bodies, theta, leaf_capacity, max_depth, far_order, G, epsilon).forces();
+}
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every,
+                                   int far_order, double G, double epsilon) {
+    check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_steps");
+    if (bodies.empty()) return;
+    BarnesHutNewtonHip<D> sim(bodies, theta, leaf_capacity, max_depth, far_order, G, epsilon);
+    sim.step(dt, nsteps, rebuild_every);
+    sim.download(bodies);
+}
+template std::vector<Vector<2>> barnes_hut_hip_n_body<2>(const std::vector<Body<2>>&, double, int, int, double, double);
+template std::vector<Vector<3>> barnes_hut_hip_n_body<3>(const std::vector<Body<3>>&, double, int, int, double, double);
+template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, double, double);
+template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int, double, double);
+template std::vector<Vector<2>> barnes_hut_hip_adaptive_n_body<2>(const std::vector<Body<2>>&, double, int, int, int, double, double);
+template std::vector<Vector<3>> barnes_hut_hip_adaptive_n_body<3>(const std::vector<Body<3>>&, double, int, int, int, double, double);
+template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int, double, double);
+template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int, double, double);
 
 template std::vector<Vector<2>> barnes_hut_hip_adaptive_n_body<2>(const std::vector<Body<2>>&, double, int, int, int);
 template std::vector<Vector<3>> barnes_hut_hip_adaptive_n_body<3>(const std::vector<Body<3>>&, double, int, int, int);

@@ -30,7 +30,8 @@ struct LeafLists {
 enum class LeafLaw : int {
     Brute = 0,     // methods.cpp:21-37   repulsive, r^2 < 1e-10 skipped
     TreeLeaf = 1,  // octree.cpp:105-125, bvh.cpp:150-176   attractive, r^2 < 1e-9 skipped
-    FmmP2P = 2     // fmm_parlay.cpp:992-1020   attractive, identical positions skipped, r^2 < 1e-10 smoothed by (1e-5)^2
+    FmmP2P = 2,    // fmm_parlay.cpp:992-1020   attractive, identical positions skipped, r^2 < 1e-10 smoothed by (1e-5)^2
+    Newton = 3     // extension (NBX_LAW_NEWTON): attractive m_j d / (r^2 + eps^2)^(3/2), every pair counted; plans only, needs set_softening
 };
 
 // Forces from the listed leaf pairs only (zero for bodies in no leaf).  Throws std::runtime_error on invalid lists or
@@ -59,6 +60,8 @@ public:
     void download(std::vector<Body<D>>& bodies);
     // 0 (NBX_FAR_MONOPOLE, every object's start) or 1 (NBX_FAR_QUADRUPOLE): the far cells' second-order term (nbx_leaf_plan_set_far_order)
     void set_far_order(int order);
+    // the softening length of LeafLaw::Newton (nbx_leaf_plan_set_softening): 0 (every object's start) or in [1e-6, 1e15]
+    void set_softening(double epsilon);
     float single_launch_ms(LeafLaw law, double G);      // pair kernel of one evaluation
     float back_to_back_ms(LeafLaw law, int reps);      // measurement: mean of the second half of `reps` launches in a row
 private:
@@ -114,6 +117,47 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
 // leaves and largest leaf of the adaptive tree the device builds from `bodies` (what nbody_sim --leaf-cap reports)
 template <int D>
 void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, std::size_t* n_leaves, std::size_t* largest_leaf);
+
+// ---- softened Newtonian gravity through the tree (extension; NBX_LAW_NEWTON) ----
+// The four calls above under F_i = +G m_i sum_j m_j d / (r^2 + epsilon^2)^(3/2): the same trees, lists and far orders, with the
+// caller's G and a softening length epsilon > 0 (nbx_leaf_plan_set_softening).  Throw std::runtime_error on failure, epsilon = 0 included.
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_n_body(const std::vector<Body<D>>& bodies, double theta, int depth, int far_order, double G, double epsilon);
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, double G, double epsilon);
+template <int D>
+std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, int far_order, double G,
+                                                      double epsilon);
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every,
+                                   int far_order, double G, double epsilon);
+
+// The same system kept on the device between chunks of steps: a context with the bodies and a plan with the octree built from them
+// (leaf_capacity < 0: fixed depth, depth 0 = barnes_hut_hip_depth; otherwise the adaptive tree down to `depth`).  energy() is the
+// context's (nbx_ctx_energy) under the Newtonian law and the same epsilon -- the context's own law and softening are set for that
+// call alone; the forces and the steps are the plan's.
+template <int D>
+class BarnesHutNewtonHip {
+public:
+    BarnesHutNewtonHip(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int depth, int far_order, double G, double epsilon);
+    ~BarnesHutNewtonHip();
+    BarnesHutNewtonHip(const BarnesHutNewtonHip&) = delete;
+    BarnesHutNewtonHip& operator=(const BarnesHutNewtonHip&) = delete;
+    std::vector<Vector<D>> forces();                          // of the bodies as they stand, on the tree as it stands
+    void step(double dt, int nsteps, int rebuild_every = 1);  // nbx_leaf_plan_step_octree
+    void energy(double* kinetic, double* potential);          // synchronises
+    void download(std::vector<Body<D>>& bodies);
+private:
+    struct nbx_ctx* ctx_ = nullptr;
+    struct nbx_leaf_plan* plan_ = nullptr;
+    std::size_t n_ = 0;
+    double G_ = 0.0;
+};
+
+// The yardstick of the Newtonian rows: the same law summed over ALL pairs by a context (nbx_ctx_set_law(NBX_FORCE_LAW_NEWTON),
+// nbx_ctx_set_softening, nbx_ctx_compute_accel, nbx_ctx_get_forces) -- no tree, no plan.
+template <int D>
+std::vector<Vector<D>> newton_all_pairs_forces_hip(const std::vector<Body<D>>& bodies, double G, double epsilon);
 
 // kernel time of the most recent leaf_pair_direct_forces_hip call on this thread (ms)
 float last_leaf_pair_kernel_ms();

@@ -363,6 +363,101 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
         }
     }
 
+    // Softened Newtonian gravity through the same trees: `-m t --law newton --softening e` (extension; NBX_LAW_NEWTON).  The rows above
+    // stay as they are; behind them come BarnesHut_HIP_newton[_quad] (BarnesHut_HIP_adaptive_newton[_quad] with --leaf-cap), timed like
+    // them, with G from --G.  Their yardstick is the context's own all-pairs evaluation of the same law (nbx_ctx_get_forces): median and
+    // 99th percentile of |F - F_all_pairs| / |F_all_pairs|.  --steps k adds a step loop that rebuilds the tree every step, and
+    // --energy-every j makes it print the Leapfrog loop's energy lines (the context's energy under the same law).
+    if (m.find('t') != std::string::npos && opt.law == "newton") {
+        const bool adaptive = opt.leaf_cap > 0;
+        const int capacity = adaptive ? opt.leaf_cap : -1;
+        const int depth = adaptive ? (opt.depth > 0 ? opt.depth : 10) : (opt.depth > 0 ? opt.depth : barnes_hut_hip_depth(static_cast<std::size_t>(n), D));
+        const std::string base_name = adaptive ? "BarnesHut_HIP_adaptive_newton" : "BarnesHut_HIP_newton";
+        Forces exact;
+        if (!(opt.softening > 0.0)) {
+            out << "Barnes-Hut on HIP under the Newtonian law needs --softening > 0: skipped" << std::endl << std::endl;
+        } else if (safely_execute(log, base_name + "_all_pairs", [&] {
+                       exact = newton_all_pairs_forces_hip<D>(bodies, opt.G, opt.softening);
+                       return 0;
+                   }) >= 0) {
+            for (int order = 0; order <= opt.far_order; ++order) {
+                const std::string name = base_name + (order ? "_quad" : "");
+                out << "Barnes-Hut on HIP, softened Newtonian law (G = " << opt.G << ", softening = " << opt.softening << "; "
+                    << (adaptive ? "adaptive octree, at most " + std::to_string(opt.leaf_cap) + " bodies per leaf down to depth " : "octree of depth ") << depth
+                    << ", theta " << opt.theta << (order ? ", far cells with their second moments" : "") << "):" << std::endl;
+                Forces forces;
+                const long long us = safely_execute(log, name, [&] {
+                    forces = adaptive ? barnes_hut_hip_adaptive_n_body<D>(bodies, opt.theta, opt.leaf_cap, depth, order, opt.G, opt.softening)
+                                      : barnes_hut_hip_n_body<D>(bodies, opt.theta, depth, order, opt.G, opt.softening);
+                    return 0;
+                });
+                if (us < 0) continue;
+                const double seconds = static_cast<double>(us) / 1e6;
+                csv << name << "," << n << "," << D;
+                write_time(csv, seconds);
+                if (opt.accuracy) csv << ",";      // the reference's Accuracy(%) is a figure of the reference law
+                csv << std::endl;
+                out << "Time taken: " << seconds << " s" << std::endl;
+                std::vector<double> rel;
+                rel.reserve(forces.size());
+                for (std::size_t i = 0; i < forces.size(); ++i) {
+                    double d2 = 0.0, f2 = 0.0;
+                    for (int k = 0; k < D; ++k) {
+                        d2 += (forces[i][k] - exact[i][k]) * (forces[i][k] - exact[i][k]);
+                        f2 += exact[i][k] * exact[i][k];
+                    }
+                    if (f2 > 0.0) rel.push_back(std::sqrt(d2 / f2));
+                }
+                if (!rel.empty()) {
+                    std::sort(rel.begin(), rel.end());
+                    out << "Newtonian relative force error against the all-pairs forces of the same law: median " << std::scientific << std::setprecision(3)
+                        << rel[rel.size() / 2] << ", 99th percentile " << rel[std::min(rel.size() - 1, rel.size() * 99 / 100)] << std::fixed
+                        << std::setprecision(6) << std::endl;
+                }
+                print_validation_forces<D>(forces, n, log);
+                print_validation_forces<D>(forces, n, std::cout);
+                if (!opt.dump.empty()) dump_raw(opt.dump + "_" + name + ".f64", forces);
+                if (opt.steps > 0) {
+                    std::vector<Body<D>> state = bodies;
+                    const long long step_us = safely_execute(log, name + "_steps", [&] {
+                        BarnesHutNewtonHip<D> sim(bodies, opt.theta, capacity, depth, order, opt.G, opt.softening);
+                        double ke = 0.0, pe = 0.0, e0 = 0.0;
+                        const int chunk = opt.energy_every > 0 ? opt.energy_every : opt.steps;
+                        if (opt.energy_every > 0) {
+                            sim.energy(&ke, &pe);
+                            e0 = ke + pe;
+                            out << "step 0  E = " << std::setprecision(12) << e0 << "  (kinetic " << ke << ", potential " << pe << ")" << std::endl;
+                        }
+                        for (int done = 0; done < opt.steps;) {
+                            const int k = std::min(chunk, opt.steps - done);
+                            sim.step(opt.dt, k, 1);
+                            done += k;
+                            if (opt.energy_every > 0) {
+                                sim.energy(&ke, &pe);
+                                out << "step " << done << "  E = " << std::setprecision(12) << ke + pe << "  |dE/E0| = " << std::setprecision(3)
+                                    << std::abs((ke + pe - e0) / e0) << std::setprecision(6) << "  (kinetic " << ke << ", potential " << pe
+                                    << ", 2K/|U| " << 2.0 * ke / std::abs(pe) << ")" << std::endl;
+                            }
+                        }
+                        sim.download(state);
+                        return 0;
+                    });
+                    if (step_us >= 0) {
+                        csv << name << "_steps," << n << "," << D;
+                        write_time(csv, static_cast<double>(step_us) / 1e6);
+                        if (opt.accuracy) csv << ",";
+                        csv << std::endl;
+                        out << "Barnes-Hut on HIP (Newtonian law), " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: "
+                            << static_cast<double>(step_us) / 1e6 << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps
+                            << " ms per step, upload, download and energies included)" << std::endl;
+                        if (!opt.dump.empty()) dump_raw(opt.dump + "_" + name + "_steps.f64", state);
+                    }
+                }
+                out << std::endl;
+            }
+        }
+    }
+
     // Near-field (leaf-pair direct sums) of the tree codes on the device: `-m p`.  The tree methods themselves are out of
     // scope; this row times the step they would hand to the GPU (FMM_Parlay<D>::p2p_phase, fmm_parlay.cpp:916-1022) on a
     // fixed-depth subdivision with ~64 bodies per leaf and 3^D neighbour lists.
@@ -530,6 +625,7 @@ void usage(const char* argv0) {
               << "                      kdk = the same helpers as a synchronised kick-drift-kick leapfrog (extension, second order)" << std::endl
               << "      --law <reference|newton> Pair law of the stepping loop: the reference's r^-4 form (default) or the attractive" << std::endl
               << "                      softened Newtonian law (extension; needs --softening; Plummer velocities then use --G)" << std::endl
+              << "                      with -m t: BarnesHut_HIP_newton rows behind the reference-law rows, judged against the all-pairs forces" << std::endl
               << "      --softening <eps> Plummer softening of the stepping loop's pair law (extension; default 0 = the reference's law)" << std::endl
               << "      --leaf-cap <k>  -m t builds the ADAPTIVE octree: leaves of at most k bodies, --depth the deepest level (default 10); 0: fixed depth" << std::endl
               << "      --far-order <0|1> 1: -m t runs its rows again with the far cells' second moments (quadrupole term; rows named ..._quad)" << std::endl

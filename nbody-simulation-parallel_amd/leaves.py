@@ -382,11 +382,16 @@ def cell_moments(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, cell_f
     return M, com, Q
 
 
-def far_correction(R: np.ndarray, M, Q: np.ndarray) -> np.ndarray:
+def far_correction(R: np.ndarray, M, Q: np.ndarray, law: str = "reference", eps: float = 0.0) -> np.ndarray:
     """What a cell of mass M and central second moments Q (stored order) adds to the monopole term M R / r^4 for a target at
     -R from its centre of mass (R = com - p_i), per unit G m_i:
         (M / r^4) [ R (-2 tr(q) / r^2 + 12 R^T q R / r^4) - 4 q R / r^2 ],   q = Q / M.
+    law="newton" (NBX_LAW_NEWTON, softening length eps): what it adds to M R / rho^3, rho^2 = r^2 + eps^2 -- the second-order term of
+    the softened kernel, exactly:
+        (M / rho^3) [ R (-(3/2) tr(q) / rho^2 + (15/2) R^T q R / rho^4) - 3 q R / rho^2 ].
     R[..., dim], M[...], Q[..., dim (dim + 1) / 2] broadcast together; zeros where M == 0."""
+    if law not in ("reference", "newton"):
+        raise ValueError("law must be 'reference' or 'newton'")
     R = np.asarray(R)
     dim = R.shape[-1]
     pairs = _quad_pairs(dim)
@@ -402,15 +407,23 @@ def far_correction(R: np.ndarray, M, Q: np.ndarray) -> np.ndarray:
         if a != b:
             qR[..., b] += q[..., k] * R[..., a]
     RqR = (R * qR).sum(axis=-1)
+    if law == "newton":
+        rho2 = r2 + R.dtype.type(eps) ** 2
+        scalar = -1.5 * tr / rho2 + 7.5 * RqR / rho2 ** 2
+        out = (M / (rho2 * np.sqrt(rho2)))[..., None] * (R * scalar[..., None] - 3 * qR / rho2[..., None])
+        return np.where(live[..., None], out, 0)
     scalar = -2 * tr / r2 + 12 * RqR / r2 ** 2
     out = (M / r2 ** 2)[..., None] * (R * scalar[..., None] - 4 * qR / r2[..., None])
     return np.where(live[..., None], out, 0)
 
 
 def far_sums(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, cell_first_leaf, cell_leaf_count, far_offsets, far_cells,
-             order: int = 0, moments=None) -> np.ndarray:
+             order: int = 0, moments=None, law: str = "reference", eps: float = 0.0) -> np.ndarray:
     """Every body's far sum per unit G m_i, fp64: sum over the cells c of its leaf's far list of M_c R / r^4 (order 0), plus
-    far_correction (order 1).  No special case of any law is applied: far pairs are far.  moments: cell_moments' result, if at hand."""
+    far_correction (order 1); law="newton": of M_c R / (r^2 + eps^2)^(3/2) and that law's far_correction.  No special case of any
+    law is applied: far pairs are far.  moments: cell_moments' result, if at hand."""
+    if law not in ("reference", "newton"):
+        raise ValueError("law must be 'reference' or 'newton'")
     lo, lb = np.asarray(leaf_offsets, dtype=np.int64), np.asarray(leaf_bodies, dtype=np.int64)
     fo, fc = np.asarray(far_offsets, dtype=np.int64), np.asarray(far_cells, dtype=np.int64)
     M, com, Q = moments if moments is not None else cell_moments(bodies, dim, lo, lb, cell_first_leaf, cell_leaf_count)
@@ -422,8 +435,45 @@ def far_sums(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, cell_first
             continue
         R = com[None, c, :] - bodies[ids, None, :dim]
         r2 = (R * R).sum(axis=2)
-        term = (M[c] / r2 ** 2)[..., None] * R
+        if law == "newton":
+            rho2 = r2 + float(eps) ** 2
+            term = (M[c] / (rho2 * np.sqrt(rho2)))[..., None] * R
+        else:
+            term = (M[c] / r2 ** 2)[..., None] * R
         if order == 1:
-            term = term + far_correction(R, M[None, c], Q[None, c, :])
+            term = term + (far_correction(R, M[None, c], Q[None, c, :], law, eps) if law == "newton" else far_correction(R, M[None, c], Q[None, c, :]))
         out[ids] = term.sum(axis=1)
     return out
+
+
+def near_sums(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, list_offsets, list_sources, eps: float):
+    """The leaf sums of NBX_LAW_NEWTON per unit G m_i, fp64, plain numpy: for every body i of target leaf t,
+        sum over the bodies j of the leaves on t's list (in list order; a repeated leaf counts twice) of m_j d / (r^2 + eps^2)^(3/2),
+    d = p_j - p_i.  Every pair counts; i == j and coincident bodies add exactly 0.  Returns (sums[n, dim], S[n]) with the
+    magnitude sums S_i = sum |m_j| |d| / (r^2 + eps^2)^(3/2), the scale of a backward-error bound on the fp32 pair terms.  Bodies
+    in no leaf get zeros."""
+    lo, lb = np.asarray(leaf_offsets, dtype=np.int64), np.asarray(leaf_bodies, dtype=np.int64)
+    so, ss = np.asarray(list_offsets, dtype=np.int64), np.asarray(list_sources, dtype=np.int64)
+    x, m = np.asarray(bodies[:, :dim], dtype=np.float64), np.asarray(bodies[:, -1], dtype=np.float64)
+    e2 = float(eps) ** 2
+    out, S = np.zeros((bodies.shape[0], dim)), np.zeros(bodies.shape[0])
+    for t in range(lo.size - 1):
+        ids = lb[lo[t]:lo[t + 1]]
+        if not ids.size or so[t + 1] == so[t]:
+            continue
+        src = np.concatenate([lb[lo[l]:lo[l + 1]] for l in ss[so[t]:so[t + 1]]])
+        if not src.size:
+            continue
+        xi = [x[ids, k][:, None] for k in range(dim)]
+        for j0 in range(0, src.size, 8192):                       # bounded temporaries: [targets, 8192] per component
+            sj = src[j0:j0 + 8192]
+            d = [x[sj, k][None, :] - xi[k] for k in range(dim)]
+            r2 = d[0] * d[0]
+            for k in range(1, dim):
+                r2 += d[k] * d[k]
+            rho2 = r2 + e2
+            w = m[None, sj] / (rho2 * np.sqrt(rho2))
+            for k in range(dim):
+                out[ids, k] += np.einsum("ij,ij->i", w, d[k])
+            S[ids] += np.einsum("ij,ij->i", np.abs(w), np.sqrt(r2))
+    return out, S

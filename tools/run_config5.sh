@@ -9,6 +9,9 @@
 #                                              # (median nearest neighbour 1230), t_dyn = 100, 1000 steps = 5 t_dyn
 #   LAW=newton SOFTENING=600 G=0.1 tools/run_config5.sh   # the same sphere under the attractive softened Newtonian law:
 #                                              # a stationary solution (t_dyn = sqrt(a^3/(G M)) = 100), energy and virial ratio hold
+#   METHOD=tree LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # the same sphere through the adaptive Barnes-Hut tree on
+#                                              # one GPU (-m t --leaf-cap 32 --far-order 1): its BarnesHut_HIP_adaptive_newton[_quad] rows,
+#                                              # step loops and energy lines; segments (LOAD, E0) are the all-pairs loop's alone
 # A run can be cut into segments where a job may not last 1000 steps (one GPU: 3.5 s per step):
 #   STEPS=250 DUMP=seg1 tools/run_config5.sh
 #   STEPS=250 LOAD=seg1_Leapfrog_HIP.f64 STEP_OFFSET=250 E0=<E of step 0> DUMP=seg2 tools/run_config5.sh   ... and so on;
@@ -24,6 +27,7 @@ EVERY="${EVERY:-50}"
 G="${G:-0.05}"
 SOFTENING="${SOFTENING:-0}"
 LAW="${LAW:-reference}"
+METHOD="${METHOD:-brute}"            # brute = the all-pairs loop (-m g); tree = the adaptive octree on one GPU (-m t --leaf-cap 32 --far-order 1)
 INTEGRATOR="${INTEGRATOR:-kd}"       # kd = the reference helpers' order (kick, drift); kdk = synchronised leapfrog (extension)
 LOAD="${LOAD:-}"; STEP_OFFSET="${STEP_OFFSET:-0}"; E0="${E0:-}"; DUMP="${DUMP:-}"
 OUT="${OUT:-gpurun_out/config5_${GPUS}gpu_${STEPS}steps.log}"
@@ -33,6 +37,14 @@ if [ -n "$DEVICES" ]; then where=(--devices "$DEVICES"); else where=(--gpus "$GP
 [ -n "$LOAD" ] && where+=(--load "$LOAD" --step-offset "$STEP_OFFSET")
 [ -n "$E0" ] && where+=(--e0 "$E0")
 [ -n "$DUMP" ] && where+=(--dump "$DUMP")
+if [ "$METHOD" = tree ]; then
+    ./nbody_sim -N "$N" -d 3 -m t --leaf-cap 32 --far-order 1 --init plummer --seed 5 --G "$G" --law "$LAW" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" | tee "$OUT"
+    grep -E "^step |Time taken|relative force error|ms per step" "$OUT" > "${OUT%.log}.summary.txt"
+    echo "summary: ${OUT%.log}.summary.txt"
+    exit 0
+elif [ "$METHOD" != brute ]; then
+    echo "METHOD must be brute or tree" >&2; exit 1
+fi
 ./nbody_sim -N "$N" -d 3 -m g --init plummer --seed 5 --G "$G" --law "$LAW" --integrator "$INTEGRATOR" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" "${where[@]}" | tee "$OUT"
 grep -E "^step |Time taken|Kernel time" "$OUT" > "${OUT%.log}.summary.txt"
 echo "summary: ${OUT%.log}.summary.txt"
