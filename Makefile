@@ -8,6 +8,9 @@ ARCH     ?= gfx950
 # -fvisibility=hidden: the shared library exports the entry points of include/nbody_hip.h and nothing else
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function -Iinclude
 LIB      := $(PKG)/libnbody_hip.so
+# A/B builds (tools/build_ab_*.sh): `make lib LIB=<other .so> O=<suffix>.o <defines>` compiles every object again under another
+# name and links it into another library; this file stays the only list of objects
+O        := .o
 
 # host side: the reference's own flags (nbody-sim-new/Makefile:1-3)
 CXX      ?= g++
@@ -18,8 +21,8 @@ all: lib oracle nbody_sim
 
 lib: $(LIB)
 
-OBJS := $(CSRC)/force_kernel.o $(CSRC)/force_sym_kernel.o $(CSRC)/force_launch.o \
-        $(CSRC)/state_kernels.o $(CSRC)/nbx_api.o $(CSRC)/nbx_node.o $(CSRC)/leaf_pair_kernel.o $(CSRC)/leaf_far_kernel.o $(CSRC)/octree_device.o $(CSRC)/close_hash.o $(CSRC)/measure_kernels.o
+OBJS := $(addprefix $(CSRC)/,$(addsuffix $(O),force_kernel force_sym_kernel force_launch state_kernels nbx_api nbx_node leaf_pair_kernel \
+          leaf_plan_api leaf_far_kernel octree_device close_hash measure_kernels))
 # name of the force-kernel variant used when the caller does not pick one
 # (round 4: the three-level summation build -- same pair arithmetic, fp32 errors ~3x smaller for +1.5 % time)
 DEFAULT_VARIANT ?= fastpk3l_t8_w3_u4
@@ -30,41 +33,46 @@ SYM_DEFAULT ?= 1
 DEFAULT_EXACT_VARIANT ?= lds_t1_w8_exact_u8
 
 # -fno-slp-vectorize: the packed arithmetic is written by hand on float2 values (see force_kernel.hip)
-$(CSRC)/force_kernel.o: $(CSRC)/force_kernel.hip $(CSRC)/nbx_internal.h
+$(CSRC)/force_kernel$(O): $(CSRC)/force_kernel.hip $(CSRC)/nbx_internal.h
 	$(HIPCC) $(HIPFLAGS) $(FORCE_KERNEL_DEFS) -fno-slp-vectorize -c $< -o $@
 
 # the symmetric own-shard pass: same flags as the one-sided force kernels
-$(CSRC)/force_sym_kernel.o: $(CSRC)/force_sym_kernel.hip $(CSRC)/sym_plan.h $(CSRC)/nbx_internal.h
+$(CSRC)/force_sym_kernel$(O): $(CSRC)/force_sym_kernel.hip $(CSRC)/sym_plan.h $(CSRC)/nbx_internal.h
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
-$(CSRC)/force_launch.o: $(CSRC)/force_launch.hip $(CSRC)/nbx_internal.h $(CSRC)/sym_plan.h Makefile
+$(CSRC)/force_launch$(O): $(CSRC)/force_launch.hip $(CSRC)/nbx_internal.h $(CSRC)/sym_plan.h Makefile
 	$(HIPCC) $(HIPFLAGS) -DNBX_DEFAULT_VARIANT='"$(DEFAULT_VARIANT)"' -DNBX_DEFAULT_EXACT_VARIANT='"$(DEFAULT_EXACT_VARIANT)"' -c $< -o $@
 
 # -ffp-contract=off: the fp64 kick/drift must round like the reference's two-step arithmetic
-$(CSRC)/state_kernels.o: $(CSRC)/state_kernels.hip $(CSRC)/nbx_internal.h
+$(CSRC)/state_kernels$(O): $(CSRC)/state_kernels.hip $(CSRC)/nbx_internal.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 
-$(CSRC)/nbx_api.o: $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h Makefile
+$(CSRC)/nbx_api$(O): $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h $(CSRC)/device_block.h include/nbody_hip.h Makefile
 	$(HIPCC) $(HIPFLAGS) -DNBX_SYM_DEFAULT=$(SYM_DEFAULT) -c $< -o $@
 
-$(CSRC)/nbx_node.o: $(CSRC)/nbx_node.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
+$(CSRC)/nbx_node$(O): $(CSRC)/nbx_node.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/measure_kernels.o: $(CSRC)/measure_kernels.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
+$(CSRC)/measure_kernels$(O): $(CSRC)/measure_kernels.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/close_hash.o: $(CSRC)/close_hash.hip $(CSRC)/nbx_internal.h $(CSRC)/device_sort.h
+$(CSRC)/close_hash$(O): $(CSRC)/close_hash.hip $(CSRC)/nbx_internal.h $(CSRC)/device_sort.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/leaf_pair_kernel.o: $(CSRC)/leaf_pair_kernel.hip $(CSRC)/leaf_plan.h $(CSRC)/leaf_plan_device.h $(CSRC)/leaf_law.h $(CSRC)/leaf_far.h $(CSRC)/octree_device.h $(CSRC)/device_sort.h $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
+# the near field of a leaf plan: the pair kernels and their launches (leaf_near.h) ...
+$(CSRC)/leaf_pair_kernel$(O): $(CSRC)/leaf_pair_kernel.hip $(CSRC)/leaf_near.h $(CSRC)/leaf_plan.h $(CSRC)/leaf_law.h $(CSRC)/nbx_internal.h include/nbody_hip.h
+	$(HIPCC) $(HIPFLAGS) $(LEAF_DEFS) -c $< -o $@
+
+# ... and the host side behind the C ABI: the one-shot call and nbx_leaf_plan_* (with the device planner's kernels, leaf_plan_device.h)
+$(CSRC)/leaf_plan_api$(O): $(CSRC)/leaf_plan_api.hip $(CSRC)/leaf_near.h $(CSRC)/leaf_plan.h $(CSRC)/leaf_plan_device.h $(CSRC)/leaf_far.h $(CSRC)/octree_device.h $(CSRC)/device_sort.h $(CSRC)/device_block.h $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) $(LEAF_DEFS) -c $< -o $@
 
 # the far field of a leaf plan: moment and far kernels
-$(CSRC)/leaf_far_kernel.o: $(CSRC)/leaf_far_kernel.hip $(CSRC)/leaf_far.h $(CSRC)/leaf_law.h $(CSRC)/nbx_internal.h include/nbody_hip.h
+$(CSRC)/leaf_far_kernel$(O): $(CSRC)/leaf_far_kernel.hip $(CSRC)/leaf_far.h $(CSRC)/leaf_law.h $(CSRC)/nbx_internal.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the octree built on the device.  -ffp-contract=off: a body's cell index must round like the host builder's two-step arithmetic
-$(CSRC)/octree_device.o: $(CSRC)/octree_device.hip $(CSRC)/octree_device.h $(CSRC)/leaf_far.h $(CSRC)/device_sort.h
+$(CSRC)/octree_device$(O): $(CSRC)/octree_device.hip $(CSRC)/octree_device.h $(CSRC)/leaf_far.h $(CSRC)/device_sort.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 
 $(LIB): $(OBJS) $(CSRC)/libnbody_hip.map
@@ -87,7 +95,7 @@ tools/ubench_banks: tools/ubench_banks.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -f $(OBJS) $(LIB) nbody_sim tools/ubench_valu tools/ubench_banks
+	rm -f $(OBJS) $(LIB) nbody_sim tools/ubench_valu tools/ubench_banks $(CSRC)/*_ab.o $(CSRC)/*_leafab.o $(PKG)/libnbody_hip_ab.so $(PKG)/libnbody_hip_leafab.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib oracle clean

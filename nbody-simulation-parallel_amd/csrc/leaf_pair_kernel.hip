@@ -38,29 +38,14 @@
 // every output written once.  Leaves are small (the reference caps them at 100 bodies, methods.h:26), so the launch
 // is tens of thousands of short workgroups; HBM traffic is 16 B per (workgroup, source body), served mostly from L2.
 #include "../../include/nbody_hip.h"
-#include "nbx_ctx.h"
-#include "leaf_plan.h"
+#include "nbx_internal.h"
+#include "leaf_near.h"
 #include "leaf_law.h"
-#include "leaf_far.h"
-#include "leaf_plan_device.h"
-#include "octree_device.h"
 
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <new>
-#include <thread>
 #include <type_traits>
-#include <vector>
 
 using namespace nbx;
 using namespace nbx_leaf;
-
-#ifndef NBX_LEAF_PACK
-#define NBX_LEAF_PACK 1   /* 0: A/B build without packed small leaves (make LEAF_DEFS=-DNBX_LEAF_PACK=0 ...) */
-#endif
 
 namespace {
 
@@ -768,1292 +753,53 @@ FusedKernel pick_fused(int dim, int law) {
     return table[dim - 2][law];
 }
 
-// The call's device arrays are one allocation, and a tree code calls once per step with arrays of the same size: the allocation
-// of a finished call is parked (one per device, up to kArenaParkMax bytes) and taken by the next call it is large enough for --
-// hipMalloc + hipFree of ~100 MB cost 0.5 ms of a 4.4-ms call.  nbx_release_cached() frees the parked ones.
-constexpr size_t kArenaParkMax = (size_t)2 << 30;
-constexpr size_t kArenasPerDevice = 2;
-constexpr size_t kHelperCopyBytes = (size_t)4 << 20;   // staged bodies from this size on are copied by a helper thread while the launch is laid out
-struct ParkedArena { int device; char* p; size_t bytes; };
-std::mutex g_arena_mu;
-std::vector<ParkedArena> g_arenas;
-
-hipError_t take_arena(int device, size_t bytes, char** out, size_t* got) {
-    {
-        std::lock_guard<std::mutex> lock(g_arena_mu);
-        size_t best = g_arenas.size();
-        for (size_t i = 0; i < g_arenas.size(); ++i)
-            if (g_arenas[i].device == device && g_arenas[i].bytes >= bytes && (best == g_arenas.size() || g_arenas[i].bytes < g_arenas[best].bytes)) best = i;
-        if (best != g_arenas.size()) {
-            *out = g_arenas[best].p;
-            *got = g_arenas[best].bytes;
-            g_arenas.erase(g_arenas.begin() + (long)best);
-            return hipSuccess;
-        }
-    }
-    *got = bytes;
-    hipError_t e = hipMalloc((void**)out, bytes);
-    if (e == hipErrorOutOfMemory) {   // the cache itself may be what is in the way: give the parked blocks back and try once more
-        (void)hipGetLastError();
-        nbx::release_parked_leaf_arenas();
-        e = hipMalloc((void**)out, bytes);
-    }
-    return e;
-}
-
-void park_arena(int device, char* p, size_t bytes) {   // nothing on the device uses p any more
-    char* evicted = nullptr;
-    if (bytes <= kArenaParkMax) {
-        std::lock_guard<std::mutex> lock(g_arena_mu);
-        g_arenas.push_back(ParkedArena{device, p, bytes});
-        size_t mine = 0, smallest = g_arenas.size();
-        for (size_t i = 0; i < g_arenas.size(); ++i)
-            if (g_arenas[i].device == device) {
-                ++mine;
-                if (smallest == g_arenas.size() || g_arenas[i].bytes < g_arenas[smallest].bytes) smallest = i;
-            }
-        if (mine > kArenasPerDevice) {                      // a call takes two (bodies; everything else): keep the two largest
-            evicted = g_arenas[smallest].p;
-            g_arenas.erase(g_arenas.begin() + (long)smallest);
-        }
-    } else {
-        evicted = p;
-    }
-    if (evicted) (void)hipFree(evicted);
-}
-
-struct DeviceBuffers {   // gives back whatever the call took when it leaves, on every path
-    char* arena = nullptr;          // everything but the staged bodies
-    size_t arena_bytes = 0;
-    char* body_arena = nullptr;     // the staged Body<D> array
-    size_t body_bytes = 0;
-    hipStream_t stream = nullptr;
-    int device = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~DeviceBuffers() {
-        const bool idle = stream && hipStreamSynchronize(stream) == hipSuccess;
-        if (arena) {
-            if (idle) park_arena(device, arena, arena_bytes);
-            else (void)hipFree(arena);
-        }
-        if (body_arena) {
-            if (idle) park_arena(device, body_arena, body_bytes);
-            else (void)hipFree(body_arena);
-        }
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (idle) nbx::park_stream(device, stream);   // back to the pool (nbx_api.hip): a stream costs more than this call's kernels
-        else if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 }  // namespace
 
-namespace nbx {
-void release_parked_leaf_arenas() {
-    std::vector<ParkedArena> parked;
-    {
-        std::lock_guard<std::mutex> lock(g_arena_mu);
-        parked.swap(g_arenas);
-    }
-    int before = 0;
-    const bool have = hipGetDevice(&before) == hipSuccess;
-    for (ParkedArena& a : parked)
-        if (hipSetDevice(a.device) == hipSuccess) (void)hipFree(a.p);
-    if (have) (void)hipSetDevice(before);
-    (void)hipGetLastError();
-}
-}  // namespace nbx
+// ---- the launch interface (leaf_near.h) ----
+namespace nbx_near {
 
-// ---- device-resident plan (include/nbody_hip.h "device-resident leaf plan") ---------------------------------------------------
-// What a tree code keeps between force evaluations while its tree stands: the validated structure laid out for the kernel
-// (leaf_plan.h) and every device buffer an evaluation needs.  An evaluation is then: gather (16 B per slot from the resident
-// fp32 source copy), pair kernel, and -- only if the caller wants them on the host -- forces by body and one copy out.
-struct nbx_leaf_plan {
-    int device = 0, dim = 3, waves = 2;
-    size_t n = 0, pslots = 0, n_ops = 0, n_blocks = 0, n_subs = 0, n_packs = 0;
-    char* arena = nullptr;          // xp | sums | pslot_body | body_slot | ops | blocks | max_mass | packed leaves | packed waves
-    size_t arena_bytes = 0;         // what take_arena handed out (a parked block may be larger than asked for)
-    bool last_wait_ok = true;       // destroy: the wait for the last evaluation succeeded (else the block is freed, not parked)
-    float4* xp = nullptr;
-    double* sums = nullptr;         // [dim][pslots]
-    uint32_t* pslot_body = nullptr; // [pslots]
-    uint32_t* body_slot = nullptr;  // [n]  inverse map, 0xffffffff for a body in no leaf
-    CopyOp* ops = nullptr;
-    LeafBlock* blocks = nullptr;
-    uint32_t* max_mass = nullptr;
-    PackSub* subs = nullptr;
-    PackBlock* packs = nullptr;
-    double* forces = nullptr;       // [n][dim], allocated when a caller first asks for forces on the host
-    double* raw = nullptr;          // staged Body<D> array of nbx_leaf_plan_forces, allocated on first use
-    size_t raw_bytes = 0;
-    hipStream_t stream = nullptr;   // own stream (host-bodies path)
-    hipStream_t last_stream = nullptr;   // stream the last evaluation was ordered on
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
-    bool evaluated = false;
-    int last_law = NBX_LAW_TREE_LEAF;
-    double last_signedG = 0.0;
-    // masses of the last evaluation: a context's m64 (stride 1) or the staged bodies (offset 2 dim, stride the body's)
-    const double* last_mass = nullptr;
-    size_t last_mass_stride = 1;
-    unsigned long long last_ctx_id = 0;   // the context whose m64 last_mass points into (0: the plan's own staged bodies)
-    bool forces_in_arena = false;   // `forces` is a piece of the arena (the one-shot call's plan), not an allocation of its own
-    bool device_planned = false;    // laid out on the device (leaf_plan_device.h); false: on the host (leaf_plan.h)
-    char* raw_arena = nullptr;      // one-shot call: the staged bodies come from the parked pool instead of hipMalloc
-    size_t raw_arena_bytes = 0;
-    nbx_leaf_dev::Summary summary_host;   // the device planner's 64 bytes land here
-    // ---- the far field (nbx_leaf_plan_set_cells; leaf_far.h): cells, far lists and the moments of the last evaluation ----
-    size_t n_leaves = 0;
-    uint32_t* unit_off = nullptr;   // [n_leaves + 1] first padded slot of every leaf (in the arena; either planner leaves it there)
-    std::vector<uint32_t> unit_host;   // the host planner's copy of it (empty after the device planner: set_cells then reads it back)
-    nbx_far::FarDevice far;         // n_cells = 0: no far field, and nothing below is touched by an evaluation
-    size_t far_entries = 0;
-    char* cell_arena = nullptr;     // every array `far` names that is the cells' own
-    size_t cell_arena_bytes = 0;
-    hipEvent_t evm0 = nullptr, evm1 = nullptr, evf0 = nullptr, evf1 = nullptr;   // moment pass, far pass (created with the first cells)
-    // an evaluation has run since the cells were set: only then do cell_rec / cell_mass hold moments.  plan_release_cells (every
-    // set_cells, destroy) clears it; nbx_leaf_plan_get_cells and the far pass of nbx_leaf_plan_time_kernel rely on that.
-    bool cells_evaluated = false;
-    bool cells_timed = false;       // ... and it recorded the four events
-    // ---- the far field's order (nbx_leaf_plan_set_far_order): the plan's own, it outlives cells and rebuilds ----
-    int far_order = NBX_FAR_MONOPOLE;
-    // ---- NBX_LAW_NEWTON's softening length (nbx_leaf_plan_set_softening): the plan's own like the order; no other law reads it ----
-    double softening = 0.0;
-    bool quads_evaluated = false;   // the last evaluation with these cells ran at order 1: cell_quad holds its second moments
-    char* quad_arena = nullptr;     // leaf_quad, cell_quad, cell_qrec of the cells as they stand; never allocated at order 0
-    size_t quad_arena_bytes = 0;
-    // ---- a structure built on the device (nbx_leaf_plan_create_octree; octree_device.h) ----
-    bool octree = false;            // made by nbx_leaf_plan_create_octree
-    bool octree_built = false;      // ... and its last build went through (a refused rebuild leaves nothing to evaluate)
-    int octree_depth = 0;
-    double octree_theta = 0.0;
-    size_t octree_capacity = 0;     // > 0: the adaptive tree (nbx_leaf_plan_create_octree_adaptive), octree_depth its max_depth
-    char* tree_arena = nullptr;     // the builder's block: the tree, six of the eight structure arrays, scratch
-    size_t tree_arena_bytes = 0;
-    nbx_octree::TreeLayout tree_layout{};
-    nbx_octree::Tree tree;
-    nbx_octree::Counts counts_host{};     // the builder's 64 bytes land here
-    const uint32_t* list_sources_dev = nullptr;   // in the arena
-};
-
-namespace {
-// The part of the validation that stays on the host whichever planner runs: the two offset arrays (n_leaves + 1 words each; the
-// lengths of every copy come from them).
-int validate_offsets(size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves, const uint32_t* list_offsets,
-                     const uint32_t* list_sources, size_t* slots_out, size_t* n_list_out) {
-    if (n > ((size_t)1 << 31) || n_leaves > ((size_t)1 << 31)) return fail(NBX_ERR_INVALID, "too many bodies / leaves");
-    if (n_leaves && (!leaf_offsets || !list_offsets)) return fail(NBX_ERR_INVALID, "null leaf arrays");
-    const size_t slots = n_leaves ? leaf_offsets[n_leaves] : 0;
-    const size_t n_list = n_leaves ? list_offsets[n_leaves] : 0;
-    if (n_leaves && (leaf_offsets[0] != 0 || list_offsets[0] != 0)) return fail(NBX_ERR_INVALID, "CSR offsets must start at 0");
-    uint32_t bad = 0;                                    // no exit inside the loop: vectorised
-    for (size_t l = 0; l < n_leaves; ++l) bad |= (uint32_t)(leaf_offsets[l + 1] < leaf_offsets[l]) | (uint32_t)(list_offsets[l + 1] < list_offsets[l]);
-    if (bad) return fail(NBX_ERR_INVALID, "CSR offsets must be non-decreasing");
-    if ((slots && !leaf_bodies) || (n_list && !list_sources)) return fail(NBX_ERR_INVALID, "null leaf arrays");
-    *slots_out = slots;
-    *n_list_out = n_list;
-    return NBX_OK;
-}
-
-// Which planner lays a structure out.  NBODY_HIP_LEAF_PLANNER=host|device in the environment decides for every call (tests run
-// every case through both); otherwise the device takes structures from kDevicePlanFrom slots + list entries on -- below that the
-// host's few microseconds beat the device planner's ~35 launches.
-constexpr size_t kDevicePlanFrom = 65536;
-bool use_device_planner(size_t n_leaves, size_t slots, size_t n_list) {
-    if (n_leaves == 0 || slots == 0) return false;                                  // nothing to lay out: the host path's early exits
-    if (slots + n_leaves > 0xfffffff0ull || n_list > 0xfffffff0ull) return false;     // the host planner words the refusal
-    if (kPackWindowWaves * (size_t)kPackMaxSubs > 128) return false;                  // A/B builds with larger windows
-    if (const char* e = std::getenv("NBODY_HIP_LEAF_PLANNER")) {
-        if (!std::strcmp(e, "host")) return false;
-        if (!std::strcmp(e, "device")) return true;
-    }
-    return slots + n_list >= kDevicePlanFrom;
-}
-
-// Host-side validation of the CSR structure: every index the kernels will follow is checked here, before anything is launched.
-int validate_csr(size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves, const uint32_t* list_offsets,
-                 const uint32_t* list_sources, size_t* slots_out) {
-    if (n > ((size_t)1 << 31) || n_leaves > ((size_t)1 << 31)) return fail(NBX_ERR_INVALID, "too many bodies / leaves");
-    if (n_leaves && (!leaf_offsets || !list_offsets)) return fail(NBX_ERR_INVALID, "null leaf arrays");
-    const size_t slots = n_leaves ? leaf_offsets[n_leaves] : 0;
-    const size_t n_list = n_leaves ? list_offsets[n_leaves] : 0;
-    if (n_leaves && (leaf_offsets[0] != 0 || list_offsets[0] != 0)) return fail(NBX_ERR_INVALID, "CSR offsets must start at 0");
-    for (size_t l = 0; l < n_leaves; ++l)
-        if (leaf_offsets[l + 1] < leaf_offsets[l] || list_offsets[l + 1] < list_offsets[l]) return fail(NBX_ERR_INVALID, "CSR offsets must be non-decreasing");
-    if ((slots && !leaf_bodies) || (n_list && !list_sources)) return fail(NBX_ERR_INVALID, "null leaf arrays");
-    {
-        std::vector<unsigned char> seen;
-        try { seen.assign(n, 0); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
-        for (size_t s = 0; s < slots; ++s) {
-            const uint32_t b = leaf_bodies[s];
-            if (b >= n) return fail(NBX_ERR_INVALID, "leaf_bodies entry out of range");
-            if (seen[b]) return fail(NBX_ERR_INVALID, "a body may belong to at most one leaf");
-            seen[b] = 1;
-        }
-    }
-    {   // the largest entry, without an exit inside the loop (so that it is vectorised: 6.7 million entries for 65,536 BVH leaves)
-        uint32_t largest = 0;
-        for (size_t e = 0; e < n_list; ++e) largest = list_sources[e] > largest ? list_sources[e] : largest;
-        if (n_list && largest >= n_leaves) return fail(NBX_ERR_INVALID, "list_sources entry out of range");
-    }
-    *slots_out = slots;
-    return NBX_OK;
-}
-
-// plan_leaves behind the C ABI: no exception leaves it (its arrays are std::vectors), an allocation failure is NBX_ERR_ALLOC
-int lay_out_launch(const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves, const uint32_t* list_offsets, const uint32_t* list_sources,
-                   LeafPlan& plan) {
-    const char* why = nullptr;
-    try {
-        why = plan_leaves(leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, plan, NBX_LEAF_PACK != 0);
-    } catch (...) {
-        why = kPlanAllocFailed;
-    }
-    if (!why) return NBX_OK;
-    return fail(why == kPlanAllocFailed ? NBX_ERR_ALLOC : NBX_ERR_INVALID, why);
-}
-
-int create_plan(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves,
-                const uint32_t* list_offsets, const uint32_t* list_sources, size_t forces_bytes);
-
-// The caller's current HIP device is put back when an entry point of this file returns
-struct DeviceScope {
-    int before = -1;
-    DeviceScope() { if (hipGetDevice(&before) != hipSuccess) before = -1; (void)hipGetLastError(); }
-    ~DeviceScope() { if (before >= 0) (void)hipSetDevice(before); }
-};
-}  // namespace
-
-extern "C" int nbx_leaf_pair_forces(const void* bodies, size_t n, int dim, size_t stride_bytes, const uint32_t* leaf_offsets,
-                                    const uint32_t* leaf_bodies, size_t n_leaves, const uint32_t* list_offsets,
-                                    const uint32_t* list_sources, int law, double G, int device, double* forces_out,
-                                    float* kernel_ms) {
-    if (kernel_ms) *kernel_ms = 0.0f;
-    if (dim != 2 && dim != 3) return fail(NBX_ERR_INVALID, "dim must be 2 or 3");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, law == NBX_LAW_NEWTON ? "NBX_LAW_NEWTON needs a plan (nbx_leaf_plan_set_softening): the one-shot call has no softening length" : "unknown law");
-    if ((!bodies || !forces_out) && n) return fail(NBX_ERR_INVALID, "null argument");
-    const size_t min_stride = (size_t)(2 * dim + 1) * sizeof(double);
-    if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
-        return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
-    size_t slots = 0, n_list = 0;
-    if (int vrc = validate_offsets(n, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, &slots, &n_list)) return vrc;
-    if (use_device_planner(n_leaves, slots, n_list)) {
-        // the structure laid out on the device (leaf_plan_device.h): a plan for this call alone, its block and the staged bodies' from the
-        // parked pool, so that a tree code calling once per step allocates nothing
-        nbx_leaf_plan* p = nullptr;
-        int prc = create_plan(&p, device, dim, n, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, n * (size_t)dim * sizeof(double));
-        if (prc) return prc;
-        DeviceScope scope;
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = take_arena(device, n * stride_bytes + 256, &p->raw_arena, &p->raw_arena_bytes);
-        if (e != hipSuccess) { prc = nbx::fail_hip(e, "staging the bodies", __FILE__, __LINE__); nbx_leaf_plan_destroy(p); return prc; }
-        p->raw = reinterpret_cast<double*>(p->raw_arena);
-        p->raw_bytes = n * stride_bytes;
-        prc = nbx_leaf_plan_forces(p, bodies, stride_bytes, law, G, forces_out, kernel_ms);
-        nbx_leaf_plan_destroy(p);
-        return prc;
-    }
-    if (int vrc = validate_csr(n, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, &slots)) return vrc;
-    int ndev = 0;
-    int rc = nbx_device_count(&ndev);
-    if (rc != NBX_OK) return rc;
-    if (device < 0 || device >= ndev) return fail(NBX_ERR_NO_DEVICE, "device ordinal out of range");
-    if (slots == 0) {   // no leaf holds a body: every force is zero (otherwise the device array, zeroed there, is copied out whole)
-        for (size_t i = 0; i < n * (size_t)dim; ++i) forces_out[i] = 0.0;
-        return NBX_OK;
-    }
-
-    DeviceScope scope;   // the caller's current device is restored on every path
-    NBX_HIP_TRY(hipSetDevice(device));
-    DeviceBuffers d;
-    d.device = device;
-    NBX_HIP_TRY(nbx::take_stream(device, &d.stream));
-    NBX_HIP_TRY(hipEventCreate(&d.ev0));
-    NBX_HIP_TRY(hipEventCreate(&d.ev1));
-    // The bodies go to the device on a helper thread (58 MB at N = 2^20; the copy from pageable memory blocks its caller for 1 ms)
-    // while this thread lays out the launch.
-    NBX_HIP_TRY(take_arena(device, n * stride_bytes + 256, &d.body_arena, &d.body_bytes));
-    double* const raw = reinterpret_cast<double*>(d.body_arena);
-    hipError_t copy_rc = hipSuccess;
-    std::thread copier;
-    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{copier};   // before d goes, on every path
-    if (n * stride_bytes >= kHelperCopyBytes) {
-        try {
-            copier = std::thread([&]() {
-                copy_rc = hipSetDevice(device);
-                if (copy_rc == hipSuccess) copy_rc = hipMemcpyAsync(raw, bodies, n * stride_bytes, hipMemcpyHostToDevice, d.stream);
-            });
-        } catch (...) {   // no thread to be had: copy here
-        }
-    }
-    if (!copier.joinable())   // small input (a thread costs more than the copy takes), or no thread
-        NBX_HIP_TRY(hipMemcpyAsync(raw, bodies, n * stride_bytes, hipMemcpyHostToDevice, d.stream));
-
-    // ---- the layout the kernel follows (leaf_plan.h; comment at the top of this file) ----
-    static thread_local LeafPlan plan;   // a tree code calls once per step: the arrays keep their capacity (and their pages) between calls
-    if (int prc = lay_out_launch(leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, plan)) return prc;
-    const size_t pslots = plan.pslots();
-    const std::vector<uint32_t>& pslot_body = plan.pslot_body;
-    const std::vector<CopyOp>& ops = plan.ops;
-    const std::vector<LeafBlock>& blocks = plan.blocks;
-    const int waves = plan.waves;
-
-    // one allocation for the call's other device arrays (each hipFree of a large buffer costs 0.2 ms on this runtime)
-    const size_t sizes[9] = {pslots * sizeof(float4), (size_t)dim * pslots * sizeof(double), n * (size_t)dim * sizeof(double),
-                             pslots * sizeof(uint32_t), ops.size() * sizeof(CopyOp), blocks.size() * sizeof(LeafBlock), sizeof(uint32_t),
-                             plan.pack_subs.size() * sizeof(PackSub), plan.pack_blocks.size() * sizeof(PackBlock)};
-    size_t offs[9], total_bytes = 0;
-    for (int i = 0; i < 9; ++i) { offs[i] = total_bytes; total_bytes += (sizes[i] + 255) / 256 * 256 + 256; }
-    NBX_HIP_TRY(take_arena(device, total_bytes, &d.arena, &d.arena_bytes));
-    char* const arena = d.arena;
-    float4* xp = reinterpret_cast<float4*>(arena + offs[0]);
-    double* acc = reinterpret_cast<double*>(arena + offs[1]);
-    double* dforces = reinterpret_cast<double*>(arena + offs[2]);
-    uint32_t* d_pb = reinterpret_cast<uint32_t*>(arena + offs[3]);
-    CopyOp* d_ops = reinterpret_cast<CopyOp*>(arena + offs[4]);
-    LeafBlock* d_blocks = reinterpret_cast<LeafBlock*>(arena + offs[5]);
-    uint32_t* d_max_mass = reinterpret_cast<uint32_t*>(arena + offs[6]);
-    PackSub* d_subs = reinterpret_cast<PackSub*>(arena + offs[7]);
-    PackBlock* d_packs = reinterpret_cast<PackBlock*>(arena + offs[8]);
-    if (copier.joinable()) copier.join();
-    NBX_HIP_TRY(copy_rc);
-    NBX_HIP_TRY(hipMemcpyAsync(d_pb, pslot_body.data(), pslots * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    if (!ops.empty()) NBX_HIP_TRY(hipMemcpyAsync(d_ops, ops.data(), ops.size() * sizeof(CopyOp), hipMemcpyHostToDevice, d.stream));
-    if (!blocks.empty()) NBX_HIP_TRY(hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(LeafBlock), hipMemcpyHostToDevice, d.stream));
-    if (!plan.pack_blocks.empty()) {
-        NBX_HIP_TRY(hipMemcpyAsync(d_subs, plan.pack_subs.data(), sizes[7], hipMemcpyHostToDevice, d.stream));
-        NBX_HIP_TRY(hipMemcpyAsync(d_packs, plan.pack_blocks.data(), sizes[8], hipMemcpyHostToDevice, d.stream));
-    }
-    NBX_HIP_TRY(hipMemsetAsync(dforces, 0, n * (size_t)dim * sizeof(double), d.stream));
-    NBX_HIP_TRY(hipMemsetAsync(d_max_mass, 0, sizeof(uint32_t), d.stream));
-    (void)hipGetLastError();
-    const unsigned gs = (unsigned)((pslots + 255) / 256);
-    hipLaunchKernelGGL(leaf_gather_kernel, dim3(gs), dim3(256), 0, d.stream, raw, stride_bytes / sizeof(double), dim, d_pb, (uint32_t)pslots,
-                       reinterpret_cast<float*>(xp), d_max_mass);
-    NBX_HIP_TRY(hipGetLastError());
+hipError_t enqueue_near(const NearDevice& d, int dim, int law, hipStream_t s, bool fuse) {
     LeafArgs a;
-    a.xp = xp; a.pslots = (uint32_t)pslots; a.ops = d_ops; a.blocks = d_blocks; a.acc = acc; a.max_mass_bits = d_max_mass; a.eps2 = 0.0f;
-    NBX_HIP_TRY(hipEventRecord(d.ev0, d.stream));
-    if (!blocks.empty()) {   // one-leaf workgroups first: they are the long ones
-        hipLaunchKernelGGL(pick(dim, law, waves), dim3((unsigned)blocks.size()), dim3(64u * (unsigned)waves), 0, d.stream, a);
-        NBX_HIP_TRY(hipGetLastError());
-    }
-    if (!plan.pack_blocks.empty()) {
-        LeafPackArgs pa;
-        pa.xp = xp; pa.pslots = (uint32_t)pslots; pa.ops = d_ops; pa.blocks = d_packs; pa.subs = d_subs; pa.acc = acc; pa.max_mass_bits = d_max_mass; pa.eps2 = 0.0f;
-        hipLaunchKernelGGL(pick_pack(dim, law), dim3((unsigned)plan.pack_blocks.size()), dim3(64), 0, d.stream, pa);
-        NBX_HIP_TRY(hipGetLastError());
-    }
-    NBX_HIP_TRY(hipEventRecord(d.ev1, d.stream));
-    const double signedG = (law == NBX_LAW_BRUTE) ? -G : G;   // brute force: forces[i] -= f (methods.cpp:131); tree codes: += (attractive)
-    hipLaunchKernelGGL(leaf_scatter_kernel, dim3(gs), dim3(256), 0, d.stream, acc, raw, stride_bytes / sizeof(double), dim, d_pb, (uint32_t)pslots,
-                       signedG, dforces);
-    NBX_HIP_TRY(hipGetLastError());
-    NBX_HIP_TRY(hipMemcpyAsync(forces_out, dforces, n * (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    NBX_HIP_TRY(hipStreamSynchronize(d.stream));
-    if (kernel_ms) NBX_HIP_TRY(hipEventElapsedTime(kernel_ms, d.ev0, d.ev1));
-    return NBX_OK;
-}
-
-namespace {
-
-int plan_set_device(const nbx_leaf_plan* p) {
-    (void)hipGetLastError();
-    NBX_HIP_TRY(hipSetDevice(p->device));
-    return NBX_OK;
-}
-
-// Work about to be queued on `s` must see the plan's buffers as the last evaluation (possibly on another stream) left them.
-int plan_order_after_last(nbx_leaf_plan* p, hipStream_t s) {
-    if (p->last_stream && p->last_stream != s) NBX_HIP_TRY(hipStreamWaitEvent(s, p->done, 0));
-    return NBX_OK;
-}
-
-int plan_mark_done(nbx_leaf_plan* p, hipStream_t s) {
-    NBX_HIP_TRY(hipEventRecord(p->done, s));
-    p->last_stream = s;
-    return NBX_OK;
-}
-
-float plan_eps2(const nbx_leaf_plan* p) { return (float)(p->softening * p->softening); }
-
-// What an evaluation under `law` needs beyond its arguments, before anything is launched.  Only NBX_LAW_NEWTON needs anything: a
-// softening length, and masses for which the heaviest body's weight at zero distance, max|m| / eps^3, is a finite, normal fp32 number
-// (the context's rule, nbx_api.hip: neither an overflow nor an all-zero field with status OK).  mass_max < 0: not known, not checked.
-int plan_check_law(const nbx_leaf_plan* p, int law, double mass_max) {
-    if (law != NBX_LAW_NEWTON) return NBX_OK;
-    if (!(p->softening > 0.0)) return fail(NBX_ERR_STATE, "NBX_LAW_NEWTON needs a softening length (nbx_leaf_plan_set_softening)");
-    const double eps3 = (double)plan_eps2(p) * p->softening;
-    if (mass_max >= 0.0 || mass_max != mass_max) {
-        if (!(mass_max / eps3 < 1.0e38)) return fail(NBX_ERR_INVALID, "softening too small for these masses: m / eps^3 must stay finite in fp32");
-        if (mass_max > 0.0 && !(mass_max / eps3 > 1.0e-30)) return fail(NBX_ERR_INVALID, "softening too large for these masses: m / eps^3 underflows in fp32");
-    }
-    return NBX_OK;
-}
-
-// the near field: the pair kernels, which WRITE the slot-ordered sums
-int plan_launch_near(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
-    if (p->n_blocks == 0 && p->n_packs == 0) return NBX_OK;
-    if (timed) NBX_HIP_TRY(hipEventRecord(p->ev0, s));
-    LeafArgs a;
-    a.xp = p->xp; a.pslots = (uint32_t)p->pslots; a.ops = p->ops; a.blocks = p->blocks; a.acc = p->sums; a.max_mass_bits = p->max_mass;
-    a.eps2 = plan_eps2(p);
+    a.xp = d.xp; a.pslots = d.pslots; a.ops = d.ops; a.blocks = d.blocks; a.acc = d.sums; a.max_mass_bits = d.max_mass; a.eps2 = d.eps2;
     LeafPackArgs pa;
-    pa.xp = p->xp; pa.pslots = (uint32_t)p->pslots; pa.ops = p->ops; pa.blocks = p->packs; pa.subs = p->subs; pa.acc = p->sums; pa.max_mass_bits = p->max_mass;
-    pa.eps2 = a.eps2;
-    if (p->n_blocks && p->n_packs && p->waves == 1) {   // both kinds (packing implies one-wave workgroups): one launch, the one-leaf workgroups first
-        hipLaunchKernelGGL(pick_fused(p->dim, law), dim3((unsigned)(p->n_blocks + p->n_packs)), dim3(64), 0, s, a, pa, (uint32_t)p->n_blocks);
-        NBX_HIP_TRY(hipGetLastError());
-    } else {
-        if (p->n_blocks) {
-            hipLaunchKernelGGL(pick(p->dim, law, p->waves), dim3((unsigned)p->n_blocks), dim3(64u * (unsigned)p->waves), 0, s, a);
-            NBX_HIP_TRY(hipGetLastError());
-        }
-        if (p->n_packs) {
-            hipLaunchKernelGGL(pick_pack(p->dim, law), dim3((unsigned)p->n_packs), dim3(64), 0, s, pa);
-            NBX_HIP_TRY(hipGetLastError());
-        }
+    pa.xp = d.xp; pa.pslots = d.pslots; pa.ops = d.ops; pa.blocks = d.packs; pa.subs = d.subs; pa.acc = d.sums; pa.max_mass_bits = d.max_mass; pa.eps2 = d.eps2;
+    if (fuse && d.n_blocks && d.n_packs && d.waves == 1) {   // both kinds (packing implies one-wave workgroups): one launch, the one-leaf workgroups first
+        hipLaunchKernelGGL(pick_fused(dim, law), dim3((unsigned)(d.n_blocks + d.n_packs)), dim3(64), 0, s, a, pa, (uint32_t)d.n_blocks);
+        return hipGetLastError();
     }
-    if (timed) NBX_HIP_TRY(hipEventRecord(p->ev1, s));
-    return NBX_OK;
-}
-
-// The second moments' arrays for the plan's cells at order 1 (one block, kept and reused while it fits; a plan at order 0 never gets
-// here with anything to do).  The caller has made sure that nothing on the device still uses the block: every caller has waited for
-// the plan's last evaluation.
-int plan_fit_quads(nbx_leaf_plan* p) {
-    nbx_far::FarDevice& f = p->far;
-    f.order = p->far_order;
-    f.leaf_quad = nullptr; f.cell_quad = nullptr; f.cell_qrec = nullptr;
-    p->quads_evaluated = false;
-    if (p->far_order != NBX_FAR_QUADRUPOLE || !f.n_cells) return NBX_OK;
-    const size_t sizes[3] = {(size_t)f.n_leaves * 6 * sizeof(double), (size_t)f.n_cells * nbx_far::quad_count(p->dim) * sizeof(double),
-                             (size_t)f.n_cells * nbx_far::quad_rec_vecs(p->dim) * sizeof(float4)};
-    size_t offs[3], total = 0;
-    for (int i = 0; i < 3; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
-    if (!p->quad_arena || p->quad_arena_bytes < total) {
-        if (p->quad_arena) park_arena(p->device, p->quad_arena, p->quad_arena_bytes);
-        p->quad_arena = nullptr;
-        p->quad_arena_bytes = 0;
-        f.order = NBX_FAR_MONOPOLE;                     // should the allocation fail, the cells stay consistent at order 0 ...
-        NBX_HIP_TRY(take_arena(p->device, total, &p->quad_arena, &p->quad_arena_bytes));
-        f.order = p->far_order;
+    if (d.n_blocks) {
+        hipLaunchKernelGGL(pick(dim, law, d.waves), dim3((unsigned)d.n_blocks), dim3(64u * (unsigned)d.waves), 0, s, a);
+        if (const hipError_t e = hipGetLastError()) return e;
     }
-    f.leaf_quad = reinterpret_cast<double*>(p->quad_arena + offs[0]);
-    f.cell_quad = reinterpret_cast<double*>(p->quad_arena + offs[1]);
-    f.cell_qrec = reinterpret_cast<float4*>(p->quad_arena + offs[2]);
-    return NBX_OK;
+    if (d.n_packs) hipLaunchKernelGGL(pick_pack(dim, law), dim3((unsigned)d.n_packs), dim3(64), 0, s, pa);
+    return hipGetLastError();
 }
 
-// The far field (leaf_far_kernel.hip): the far terms of the plan's cells ADDED to the sums the pair kernels wrote.  `with_moments`:
-// this evaluation's moment pass ran just before (nbx_leaf_plan_time_kernel repeats the far pass on the last evaluation's).
-int plan_launch_far(nbx_leaf_plan* p, int law, hipStream_t s, bool timed, bool with_moments = true) {
-    if (!p->far.n_cells) return NBX_OK;
-    nbx_far::FarDevice f = p->far;
-    f.eps2 = plan_eps2(p);
-    if (!with_moments && !p->quads_evaluated) f.order = NBX_FAR_MONOPOLE;   // no second moments of these positions: the order the sums were made at
-    if (timed) NBX_HIP_TRY(hipEventRecord(p->evf0, s));
-    NBX_HIP_TRY(nbx_far::enqueue_far(f, p->dim, law, s));
-    if (timed) NBX_HIP_TRY(hipEventRecord(p->evf1, s));
-    p->cells_evaluated = true;
-    p->cells_timed = timed;
-    if (with_moments) p->quads_evaluated = f.order == NBX_FAR_QUADRUPOLE;
-    return NBX_OK;
+static dim3 grid256(size_t items) { return dim3((unsigned)((items + 255) / 256)); }
+
+hipError_t enqueue_gather_staged(const double* raw, size_t stride_d, int dim, const uint32_t* pslot_body, size_t pslots, float4* xp, uint32_t* max_mass,
+                                 hipStream_t s) {
+    hipLaunchKernelGGL(leaf_gather_kernel, grid256(pslots), dim3(256), 0, s, raw, stride_d, dim, pslot_body, (uint32_t)pslots, reinterpret_cast<float*>(xp), max_mass);
+    return hipGetLastError();
+}
+hipError_t enqueue_gather_resident(const float* pos, const float* mass, unsigned pad, int dim, const uint32_t* body_slot, size_t n, float4* xp,
+                                   uint32_t* max_mass, hipStream_t s) {
+    hipLaunchKernelGGL(leaf_gather_by_body_kernel, grid256(n), dim3(256), 0, s, pos, mass, pad, dim, body_slot, n, reinterpret_cast<float*>(xp), max_mass);
+    return hipGetLastError();
+}
+hipError_t enqueue_init_pads(const uint32_t* pslot_body, size_t pslots, int dim, float4* xp, hipStream_t s) {
+    hipLaunchKernelGGL(leaf_init_pads_kernel, grid256(pslots), dim3(256), 0, s, pslot_body, (uint32_t)pslots, dim, reinterpret_cast<float*>(xp));
+    return hipGetLastError();
+}
+hipError_t enqueue_scatter(const double* sums, const double* raw, size_t stride_d, int dim, const uint32_t* pslot_body, size_t pslots, double signedG,
+                           double* forces, hipStream_t s) {
+    hipLaunchKernelGGL(leaf_scatter_kernel, grid256(pslots), dim3(256), 0, s, sums, raw, stride_d, dim, pslot_body, (uint32_t)pslots, signedG, forces);
+    return hipGetLastError();
+}
+hipError_t enqueue_forces_by_body(const double* sums, size_t pslots, const uint32_t* body_slot, size_t n, int dim, double signedG, const double* mass,
+                                  size_t mass_stride, double* forces, hipStream_t s) {
+    hipLaunchKernelGGL(leaf_forces_by_body_kernel, grid256(n), dim3(256), 0, s, sums, (uint32_t)pslots, body_slot, n, dim, signedG, mass, mass_stride, forces);
+    return hipGetLastError();
 }
 
-// One evaluation's kernels behind the gather: the cells' moments from the positions just gathered, the near field, the far field.
-// A plan without cells launches the pair kernels and nothing else.
-int plan_launch_pairs(nbx_leaf_plan* p, int law, hipStream_t s, bool timed) {
-    if (p->far.n_cells) {
-        if (timed) NBX_HIP_TRY(hipEventRecord(p->evm0, s));
-        NBX_HIP_TRY(nbx_far::enqueue_moments(p->far, p->dim, s));
-        if (timed) NBX_HIP_TRY(hipEventRecord(p->evm1, s));
-    }
-    if (int rc = plan_launch_near(p, law, s, timed)) return rc;
-    return plan_launch_far(p, law, s, timed);
-}
-
-int plan_forces_out(nbx_leaf_plan* p, hipStream_t s, double* forces_out) {
-    if (p->last_ctx_id && !nbx::ctx_alive(p->last_ctx_id))   // the masses were read where the evaluation found them: in a context that is gone
-        return fail(NBX_ERR_STATE, "the context of the last evaluation no longer exists: evaluate again before asking for forces");
-    if (!p->forces && p->n) NBX_HIP_TRY(hipMalloc((void**)&p->forces, p->n * (size_t)p->dim * sizeof(double)));
-    if (p->n) {
-        hipLaunchKernelGGL(leaf_forces_by_body_kernel, dim3((unsigned)((p->n + 255) / 256)), dim3(256), 0, s, p->sums, (uint32_t)p->pslots,
-                           p->body_slot, p->n, p->dim, p->last_signedG, p->last_mass, p->last_mass_stride, p->forces);
-        NBX_HIP_TRY(hipGetLastError());
-        NBX_HIP_TRY(hipMemcpyAsync(forces_out, p->forces, p->n * (size_t)p->dim * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    NBX_HIP_TRY(hipStreamSynchronize(s));
-    return NBX_OK;
-}
-
-
-#define PLAN_TRY(expr)                                                                                             \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) { const int r_ = nbx::fail_hip(e_, #expr, __FILE__, __LINE__); nbx_leaf_plan_destroy(p); return r_; } \
-    } while (0)
-
-// The plan's buffers on the device, laid out there (leaf_plan_device.h): the four CSR arrays go over as they are, ~35 kernels build
-// what plan_leaves builds on the host, 64 bytes come back.  forces_bytes > 0 reserves the one-shot call's force array in the same block.
-int create_plan_on_device(nbx_leaf_plan* p, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves, const uint32_t* list_offsets,
-                          const uint32_t* list_sources, size_t slots, size_t n_list, size_t forces_bytes) {
-    using namespace nbx_leaf_dev;
-    const Bounds b{p->n, n_leaves, slots, n_list};
-    const Layout L = make_layout(b, p->dim);
-    const size_t forces_off = L.total;
-    const size_t total = L.total + (forces_bytes ? (forces_bytes + 255) / 256 * 256 + 256 : 0);
-    PLAN_TRY(take_arena(p->device, total, &p->arena, &p->arena_bytes));
-    const DevicePlan d = plan_pointers(p->arena, L);
-    p->xp = d.xp; p->sums = d.sums; p->pslot_body = d.pslot_body; p->body_slot = d.body_slot; p->ops = d.ops; p->blocks = d.blocks;
-    p->subs = d.subs; p->packs = d.packs; p->max_mass = d.max_mass;
-    p->unit_off = reinterpret_cast<uint32_t*>(p->arena + L.unit_off);
-    if (forces_bytes) { p->forces = reinterpret_cast<double*>(p->arena + forces_off); p->forces_in_arena = true; }
-    PLAN_TRY(enqueue_device_plan(b, p->dim, leaf_offsets, leaf_bodies, list_offsets, list_sources, NBX_LEAF_PACK != 0, p->arena, L, p->stream, &p->summary_host));
-    PLAN_TRY(hipStreamSynchronize(p->stream));
-    const Summary& S = p->summary_host;
-    if (S.err != kErrNone) {
-        const uint32_t code = S.err;
-        nbx_leaf_plan_destroy(p);
-        return fail(NBX_ERR_INVALID, error_text(code));
-    }
-    p->device_planned = true;
-    p->waves = (int)S.waves; p->pslots = S.pslots; p->n_ops = S.n_ops; p->n_blocks = S.n_blocks; p->n_subs = S.n_subs; p->n_packs = S.n_packs;
-    return NBX_OK;
-}
-
-int create_plan_on_host(nbx_leaf_plan* p, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves, const uint32_t* list_offsets,
-                        const uint32_t* list_sources, size_t forces_bytes) {
-    const size_t n = p->n;
-    const int dim = p->dim;
-    LeafPlan host;
-    if (int prc = lay_out_launch(leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, host)) { nbx_leaf_plan_destroy(p); return prc; }
-    p->waves = host.waves;
-    p->pslots = host.pslots(); p->n_ops = host.ops.size(); p->n_blocks = host.blocks.size();
-    p->n_subs = host.pack_subs.size(); p->n_packs = host.pack_blocks.size();
-    std::vector<uint32_t> body_slot;
-    try { body_slot.assign(n, 0xffffffffu); } catch (...) { nbx_leaf_plan_destroy(p); return fail(NBX_ERR_ALLOC, "host allocation failed"); }
-    for (size_t s = 0; s < p->pslots; ++s)
-        if (host.pslot_body[s] != 0xffffffffu) body_slot[host.pslot_body[s]] = (uint32_t)s;
-    const size_t sizes[11] = {(p->pslots + 2) * sizeof(float4), (size_t)dim * p->pslots * sizeof(double), p->pslots * sizeof(uint32_t),
-                              n * sizeof(uint32_t), p->n_ops * sizeof(CopyOp), p->n_blocks * sizeof(LeafBlock), sizeof(uint32_t),
-                              p->n_subs * sizeof(PackSub), p->n_packs * sizeof(PackBlock), forces_bytes, host.unit_off.size() * sizeof(uint32_t)};
-    size_t offs[11], total = 0;
-    for (int i = 0; i < 11; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
-    PLAN_TRY(take_arena(p->device, total, &p->arena, &p->arena_bytes));   // a tree code makes a plan per step: the last plan's block, parked by its destroy
-    p->xp = reinterpret_cast<float4*>(p->arena + offs[0]);
-    p->sums = reinterpret_cast<double*>(p->arena + offs[1]);
-    p->pslot_body = reinterpret_cast<uint32_t*>(p->arena + offs[2]);
-    p->body_slot = reinterpret_cast<uint32_t*>(p->arena + offs[3]);
-    p->ops = reinterpret_cast<CopyOp*>(p->arena + offs[4]);
-    p->blocks = reinterpret_cast<LeafBlock*>(p->arena + offs[5]);
-    p->max_mass = reinterpret_cast<uint32_t*>(p->arena + offs[6]);
-    p->subs = reinterpret_cast<PackSub*>(p->arena + offs[7]);
-    p->packs = reinterpret_cast<PackBlock*>(p->arena + offs[8]);
-    if (forces_bytes) { p->forces = reinterpret_cast<double*>(p->arena + offs[9]); p->forces_in_arena = true; }
-    p->unit_off = reinterpret_cast<uint32_t*>(p->arena + offs[10]);   // the far field's passes walk the leaves' slots by it (leaf_far.h)
-    if (sizes[10]) PLAN_TRY(hipMemcpyAsync(p->unit_off, host.unit_off.data(), sizes[10], hipMemcpyHostToDevice, p->stream));
-    if (p->n_packs) {
-        PLAN_TRY(hipMemcpyAsync(p->subs, host.pack_subs.data(), sizes[7], hipMemcpyHostToDevice, p->stream));
-        PLAN_TRY(hipMemcpyAsync(p->packs, host.pack_blocks.data(), sizes[8], hipMemcpyHostToDevice, p->stream));
-    }
-    if (p->pslots) PLAN_TRY(hipMemcpyAsync(p->pslot_body, host.pslot_body.data(), sizes[2], hipMemcpyHostToDevice, p->stream));
-    if (n) PLAN_TRY(hipMemcpyAsync(p->body_slot, body_slot.data(), sizes[3], hipMemcpyHostToDevice, p->stream));
-    if (p->n_ops) PLAN_TRY(hipMemcpyAsync(p->ops, host.ops.data(), sizes[4], hipMemcpyHostToDevice, p->stream));
-    if (p->n_blocks) PLAN_TRY(hipMemcpyAsync(p->blocks, host.blocks.data(), sizes[5], hipMemcpyHostToDevice, p->stream));
-    PLAN_TRY(hipStreamSynchronize(p->stream));   // the host arrays above go out of scope
-    p->unit_host.swap(host.unit_off);
-    return NBX_OK;
-}
-
-// nbx_leaf_plan_create and the one-shot call's plan: validation, the layout (device or host planner), the buffers an evaluation needs.
-int create_plan(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves,
-                const uint32_t* list_offsets, const uint32_t* list_sources, size_t forces_bytes) {
-    if (!out) return fail(NBX_ERR_INVALID, "out is null");
-    *out = nullptr;
-    if (dim != 2 && dim != 3) return fail(NBX_ERR_INVALID, "dim must be 2 or 3");
-    size_t slots = 0, n_list = 0;
-    if (int vrc = validate_offsets(n, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, &slots, &n_list)) return vrc;
-    const bool on_device = use_device_planner(n_leaves, slots, n_list);
-    if (!on_device)   // the host planner follows every index: all of them are checked first (the device planner checks as it goes)
-        if (int vrc = validate_csr(n, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, &slots)) return vrc;
-    int ndev = 0;
-    int rc = nbx_device_count(&ndev);
-    if (rc != NBX_OK) return rc;
-    if (device < 0 || device >= ndev) return fail(NBX_ERR_NO_DEVICE, "device ordinal out of range");
-    nbx_leaf_plan* p = new (std::nothrow) nbx_leaf_plan();
-    if (!p) return fail(NBX_ERR_ALLOC, "host allocation failed");
-    p->device = device; p->dim = dim; p->n = n; p->n_leaves = n_leaves;
-    DeviceScope scope;
-    PLAN_TRY(hipSetDevice(device));
-    PLAN_TRY(nbx::take_stream(device, &p->stream));
-    PLAN_TRY(hipEventCreate(&p->ev0));
-    PLAN_TRY(hipEventCreate(&p->ev1));
-    PLAN_TRY(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
-    rc = on_device ? create_plan_on_device(p, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, slots, n_list, forces_bytes)
-                   : create_plan_on_host(p, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, forces_bytes);
-    if (rc) return rc;                                                    // p is gone already
-    // queued behind the layout, waited for by whoever evaluates first (plan_order_after_last): the sums of slots no workgroup
-    // writes (a leaf's pad) stay zero, and the pads of odd leaves are massless and far away (the body-major gather never touches them)
-    const size_t sum_bytes = (size_t)dim * p->pslots * sizeof(double);
-    PLAN_TRY(hipMemsetAsync(p->sums, 0, sum_bytes ? sum_bytes : 8, p->stream));
-    if (p->pslots) {
-        hipLaunchKernelGGL(leaf_init_pads_kernel, dim3((unsigned)((p->pslots + 255) / 256)), dim3(256), 0, p->stream, p->pslot_body, (uint32_t)p->pslots,
-                           dim, reinterpret_cast<float*>(p->xp));
-        PLAN_TRY(hipGetLastError());
-    }
-    if (int mrc = plan_mark_done(p, p->stream)) { nbx_leaf_plan_destroy(p); return mrc; }
-    *out = p;
-    return NBX_OK;
-}
-#undef PLAN_TRY
-
-}  // namespace
-
-namespace {
-// Gives the cells' device arrays back (parked when nothing on the device can still touch them) and forgets the cells; with
-// `events` the four timing events go too (destroy).
-void plan_release_cells(nbx_leaf_plan* p, bool device_idle, bool events) {
-    if (p->cell_arena) {
-        if (device_idle) park_arena(p->device, p->cell_arena, p->cell_arena_bytes);
-        else (void)hipFree(p->cell_arena);
-    }
-    p->cell_arena = nullptr;
-    p->cell_arena_bytes = 0;
-    p->far = nbx_far::FarDevice();
-    p->far_entries = 0;
-    p->cells_evaluated = p->cells_timed = p->quads_evaluated = false;
-    if (events) {
-        if (p->quad_arena) {                           // destroy: the block of the second moments goes too (set_cells keeps it for the next cells)
-            if (device_idle) park_arena(p->device, p->quad_arena, p->quad_arena_bytes);
-            else (void)hipFree(p->quad_arena);
-            p->quad_arena = nullptr;
-            p->quad_arena_bytes = 0;
-        }
-        hipEvent_t* const evs[4] = {&p->evm0, &p->evm1, &p->evf0, &p->evf1};
-        for (hipEvent_t* e : evs) {
-            if (*e) (void)hipEventDestroy(*e);
-            *e = nullptr;
-        }
-    }
-}
-
-// A block of at least `bytes`: the one the plan holds when it is large enough, else that one parked (the caller has made sure that
-// nothing on the device uses it) and another taken.
-int plan_fit_arena(nbx_leaf_plan* p, size_t bytes, char** arena, size_t* arena_bytes) {
-    if (*arena && *arena_bytes >= bytes) return NBX_OK;
-    if (*arena) park_arena(p->device, *arena, *arena_bytes);
-    *arena = nullptr;
-    *arena_bytes = 0;
-    NBX_HIP_TRY(take_arena(p->device, bytes, arena, arena_bytes));
-    return NBX_OK;
-}
-
-// Build (or build again) the octree of a plan made by nbx_leaf_plan_create_octree from the context's current positions, and lay the
-// plan and its far field out, all on the context's stream.  Two read-backs of 64 bytes: the builder's counts, the planner's summary.
-// A refusal leaves the plan without a structure (octree_built = false) but with its blocks, for the next build.
-int plan_build_octree(nbx_leaf_plan* p, nbx_ctx* c) {
-    using namespace nbx_leaf_dev;
-    hipStream_t s = c->stream;
-    if (int rc = plan_order_after_last(p, s)) return rc;
-    p->octree_built = false;
-    p->evaluated = false;
-    p->cells_evaluated = p->cells_timed = p->quads_evaluated = false;
-    p->far = nbx_far::FarDevice();
-    p->far_entries = 0;
-    const int dim = p->dim, depth = p->octree_depth;
-    const nbx_octree::TreeLayout& T = p->tree_layout;
-    if (int rc = plan_fit_arena(p, T.total, &p->tree_arena, &p->tree_arena_bytes)) return rc;
-    if (p->octree_capacity)
-        NBX_HIP_TRY(nbx_octree::enqueue_build_adaptive(c->x64, c->pad, p->n, dim, depth, p->octree_capacity, p->octree_theta, p->tree_arena, T, s, &p->counts_host,
-                                                       &p->tree));
-    else
-        NBX_HIP_TRY(nbx_octree::enqueue_build(c->x64, c->pad, p->n, dim, depth, p->octree_theta, p->tree_arena, T, s, &p->counts_host, &p->tree));
-    NBX_HIP_TRY(hipStreamSynchronize(s));   // the counts are here; whatever used the plan's blocks before is over
-    if (int rc = plan_mark_done(p, s)) return rc;
-    const nbx_octree::Counts C = p->counts_host;
-    if (C.bad) return fail(NBX_ERR_INVALID, "a coordinate is not finite");
-    if (C.near_entries > 0xfffffff0ull) return fail(NBX_ERR_INVALID, "near lists too long");
-    if (C.far_entries > 0xfffffff0ull) return fail(NBX_ERR_INVALID, "far lists too long");
-    // the plan's block, sized by the counts (leaf_plan_device.h)
-    const Bounds b{p->n, C.n_leaves, p->n, (size_t)C.near_entries};
-    const Layout L = make_layout(b, dim);
-    if (int rc = plan_fit_arena(p, L.total, &p->arena, &p->arena_bytes)) return rc;
-    const DevicePlan d = plan_pointers(p->arena, L);
-    p->xp = d.xp; p->sums = d.sums; p->pslot_body = d.pslot_body; p->body_slot = d.body_slot; p->ops = d.ops; p->blocks = d.blocks;
-    p->subs = d.subs; p->packs = d.packs; p->max_mass = d.max_mass;
-    p->unit_off = reinterpret_cast<uint32_t*>(p->arena + L.unit_off);
-    p->unit_host.clear();
-    p->n_leaves = C.n_leaves;
-    uint32_t* const list_sources = reinterpret_cast<uint32_t*>(p->arena + L.list_sources);
-    p->list_sources_dev = list_sources;
-    // the cells' block: far lists, the far pass's waves, the moments, the far layout's scratch
-    const size_t nc = C.n_cells, nl = C.n_leaves;
-    const size_t sizes[7] = {(size_t)C.far_entries * 4, (size_t)C.far_blocks * sizeof(nbx_far::FarBlock), nl * 4 * sizeof(double), nc * sizeof(double),
-                             nc * (size_t)dim * sizeof(double), nc * sizeof(float4), nbx_octree::far_scratch_bytes(C.far_blocks)};
-    size_t offs[7], total = 0;
-    for (int i = 0; i < 7; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
-    if (int rc = plan_fit_arena(p, total, &p->cell_arena, &p->cell_arena_bytes)) return rc;
-    for (hipEvent_t* ev : {&p->evm0, &p->evm1, &p->evf0, &p->evf1})
-        if (!*ev) NBX_HIP_TRY(hipEventCreate(ev));
-    char* const cells = p->cell_arena;
-    uint32_t* const far_cells = reinterpret_cast<uint32_t*>(cells + offs[0]);
-    nbx_far::FarBlock* const far_blocks = reinterpret_cast<nbx_far::FarBlock*>(cells + offs[1]);
-    if (p->octree_capacity)
-        NBX_HIP_TRY(nbx_octree::enqueue_fill_adaptive(p->n, dim, depth, p->octree_capacity, p->octree_theta, p->tree_arena, T, list_sources, far_cells, s));
-    else
-        NBX_HIP_TRY(nbx_octree::enqueue_fill(p->n, dim, depth, p->octree_theta, p->tree_arena, T, list_sources, far_cells, s));
-    NBX_HIP_TRY(enqueue_device_plan(b, dim, p->tree.leaf_offsets, p->tree.leaf_bodies, p->tree.list_offsets, list_sources, NBX_LEAF_PACK != 0, p->arena, L, s,
-                                    &p->summary_host, true));
-    if (nc) NBX_HIP_TRY(nbx_octree::enqueue_far_layout(p->unit_off, C, p->tree_arena, T, far_blocks, cells + offs[6], s));
-    NBX_HIP_TRY(hipStreamSynchronize(s));
-    const Summary& S = p->summary_host;
-    if (S.err != kErrNone) return fail(NBX_ERR_INVALID, error_text(S.err));
-    p->device_planned = true;
-    p->waves = (int)S.waves; p->pslots = S.pslots; p->n_ops = S.n_ops; p->n_blocks = S.n_blocks; p->n_subs = S.n_subs; p->n_packs = S.n_packs;
-    if (nc) {
-        nbx_far::FarDevice& f = p->far;
-        f.xp = p->xp; f.unit_off = p->unit_off; f.sums = p->sums;
-        f.pslots = (uint32_t)p->pslots; f.n_leaves = C.n_leaves; f.n_cells = C.n_cells;
-        f.n_small = C.n_small; f.n_big = C.n_cells - C.n_small; f.n_blocks = C.far_blocks;
-        f.cell_first = p->tree.cell_first; f.cell_count = p->tree.cell_count;
-        f.small_cells = p->tree.small_cells; f.big_cells = p->tree.small_cells + C.n_small;
-        f.far_cells = far_cells; f.blocks = far_blocks;
-        f.leaf_mom = reinterpret_cast<double*>(cells + offs[2]);
-        f.cell_mass = reinterpret_cast<double*>(cells + offs[3]);
-        f.cell_com = reinterpret_cast<double*>(cells + offs[4]);
-        f.cell_rec = reinterpret_cast<float4*>(cells + offs[5]);
-        p->far_entries = (size_t)C.far_entries;
-        if (int rc = plan_fit_quads(p)) { p->far = nbx_far::FarDevice(); p->far_entries = 0; return rc; }   // the stream is idle (synchronised above)
-    }
-    // as create_plan leaves a new plan: the sums of slots no workgroup writes are zero, the pads massless and far away
-    const size_t sum_bytes = (size_t)dim * p->pslots * sizeof(double);
-    NBX_HIP_TRY(hipMemsetAsync(p->sums, 0, sum_bytes ? sum_bytes : 8, s));
-    if (p->pslots) {
-        hipLaunchKernelGGL(leaf_init_pads_kernel, dim3((unsigned)((p->pslots + 255) / 256)), dim3(256), 0, s, p->pslot_body, (uint32_t)p->pslots, dim,
-                           reinterpret_cast<float*>(p->xp));
-        NBX_HIP_TRY(hipGetLastError());
-    }
-    p->octree_built = true;
-    return plan_mark_done(p, s);
-}
-
-int plan_needs_structure(const nbx_leaf_plan* p) {
-    if (p->octree && !p->octree_built) return fail(NBX_ERR_STATE, "the plan's last octree build was refused: rebuild it first");
-    return NBX_OK;
-}
-
-int plan_check_ctx(const nbx_leaf_plan* p, const nbx_ctx* c) {
-    if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
-        return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
-    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
-    return NBX_OK;
-}
-
-// both octree entry points: leaf_capacity = 0 is the fixed-depth tree
-int create_octree_plan(nbx_leaf_plan** out, nbx_ctx* c, int depth, size_t leaf_capacity, double theta) {
-    if (!out) return fail(NBX_ERR_INVALID, "out is null");
-    *out = nullptr;
-    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
-    if (depth < 0 || depth > nbx_octree::kMaxDepth) return fail(NBX_ERR_INVALID, "depth must be in [0, 10]");
-    if (!(theta >= 0.0) || !std::isfinite(theta)) return fail(NBX_ERR_INVALID, "theta must be finite and >= 0");
-    if (c->n_shards != 1) return fail(NBX_ERR_INVALID, "the context must be a single-shard context");
-    if (c->n_total == 0 || c->n_total > ((size_t)1 << 31)) return fail(NBX_ERR_INVALID, "the context must hold between 1 and 2^31 bodies");
-    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
-    nbx_leaf_plan* p = new (std::nothrow) nbx_leaf_plan();
-    if (!p) return fail(NBX_ERR_ALLOC, "host allocation failed");
-    p->device = c->device; p->dim = c->dim; p->n = c->n_total;
-    p->octree = true; p->octree_depth = depth; p->octree_theta = theta; p->octree_capacity = leaf_capacity;
-    p->tree_layout = nbx_octree::make_tree_layout(p->n, p->dim, depth, leaf_capacity > 0);
-    DeviceScope scope;
-    hipError_t e = hipSetDevice(p->device);
-    if (e == hipSuccess) e = nbx::take_stream(p->device, &p->stream);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->done, hipEventDisableTiming);
-    int rc = e == hipSuccess ? plan_build_octree(p, c) : nbx::fail_hip(e, "creating the plan", __FILE__, __LINE__);
-    if (rc) { nbx_leaf_plan_destroy(p); return rc; }
-    *out = p;
-    return NBX_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int nbx_leaf_plan_create_octree(nbx_leaf_plan** out, nbx_ctx* c, int depth, double theta) { return create_octree_plan(out, c, depth, 0, theta); }
-
-int nbx_leaf_plan_create_octree_adaptive(nbx_leaf_plan** out, nbx_ctx* c, int max_depth, int leaf_capacity, double theta) {
-    if (leaf_capacity < 0) {
-        if (out) *out = nullptr;
-        return fail(NBX_ERR_INVALID, out ? "leaf_capacity must be >= 0" : "out is null");
-    }
-    return create_octree_plan(out, c, max_depth, (size_t)leaf_capacity, theta);
-}
-
-int nbx_leaf_plan_rebuild_octree(nbx_leaf_plan* p, nbx_ctx* c) {
-    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (!p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
-    if (int rc = plan_check_ctx(p, c)) return rc;
-    DeviceScope scope;
-    if (int rc = plan_set_device(p)) return rc;
-    return plan_build_octree(p, c);
-}
-
-int nbx_leaf_plan_structure_sizes(const nbx_leaf_plan* p, size_t* n_leaves, size_t* near_entries, size_t* n_cells, size_t* far_entries) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (!p->octree || !p->octree_built) return fail(NBX_ERR_STATE, "the plan holds no structure built on the device");
-    if (n_leaves) *n_leaves = p->counts_host.n_leaves;
-    if (near_entries) *near_entries = (size_t)p->counts_host.near_entries;
-    if (n_cells) *n_cells = p->counts_host.n_cells;
-    if (far_entries) *far_entries = (size_t)p->counts_host.far_entries;
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_get_structure(nbx_leaf_plan* p, uint32_t* leaf_offsets, uint32_t* leaf_bodies, uint32_t* list_offsets, uint32_t* list_sources,
-                                uint32_t* cell_first_leaf, uint32_t* cell_leaf_count, uint32_t* far_offsets, uint32_t* far_cells) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (!p->octree || !p->octree_built) return fail(NBX_ERR_STATE, "the plan holds no structure built on the device");
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    const nbx_octree::Counts& C = p->counts_host;
-    const size_t nl = C.n_leaves, nc = C.n_cells;
-    // the far lists live with the cells; nbx_leaf_plan_set_cells on this plan would have replaced them
-    const uint32_t* const far_dev = p->far.n_cells == nc ? p->far.far_cells : nullptr;
-    if (far_cells && C.far_entries && !far_dev) return fail(NBX_ERR_STATE, "the plan's cells were replaced by nbx_leaf_plan_set_cells");
-    struct Piece { uint32_t* to; const uint32_t* from; size_t words; };
-    const Piece pieces[8] = {{leaf_offsets, p->tree.leaf_offsets, nl + 1}, {leaf_bodies, p->tree.leaf_bodies, p->n}, {list_offsets, p->tree.list_offsets, nl + 1},
-                             {list_sources, p->list_sources_dev, (size_t)C.near_entries}, {cell_first_leaf, p->tree.cell_first, nc},
-                             {cell_leaf_count, p->tree.cell_count, nc}, {far_offsets, p->tree.far_offsets, nl + 1}, {far_cells, far_dev, (size_t)C.far_entries}};
-    for (const Piece& piece : pieces)
-        if (piece.to && piece.words) NBX_HIP_TRY(hipMemcpyAsync(piece.to, piece.from, piece.words * 4, hipMemcpyDeviceToHost, s));
-    NBX_HIP_TRY(hipStreamSynchronize(s));
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_create(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies,
-                         size_t n_leaves, const uint32_t* list_offsets, const uint32_t* list_sources) {
-    return create_plan(out, device, dim, n, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, 0);
-}
-
-int nbx_leaf_plan_destroy(nbx_leaf_plan* p) {
-    if (!p) return NBX_OK;
-    DeviceScope scope;
-    (void)hipSetDevice(p->device);
-    // the last evaluation may have been queued on a context's stream, and that context may be gone by now (its stream with it):
-    // wait on the plan's own event, which every piece of work queued on a foreign stream is followed by
-    p->last_wait_ok = !(p->last_stream && p->done) || hipEventSynchronize(p->done) == hipSuccess;
-    bool idle = p->stream && hipStreamSynchronize(p->stream) == hipSuccess;
-    plan_release_cells(p, idle && p->last_wait_ok, true);
-    if (p->arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->arena, p->arena_bytes); else (void)hipFree(p->arena); }
-    if (p->tree_arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->tree_arena, p->tree_arena_bytes); else (void)hipFree(p->tree_arena); }
-    if (p->forces && !p->forces_in_arena) (void)hipFree(p->forces);
-    if (p->raw_arena) { if (idle && p->last_wait_ok) park_arena(p->device, p->raw_arena, p->raw_arena_bytes); else (void)hipFree(p->raw_arena); }
-    else if (p->raw) (void)hipFree(p->raw);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
-    if (p->done) (void)hipEventDestroy(p->done);
-    if (p->stream) { if (idle) nbx::park_stream(p->device, p->stream); else (void)hipStreamDestroy(p->stream); }
-    (void)hipGetLastError();
-    delete p;
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_info(const nbx_leaf_plan* p, size_t* slots, size_t* runs, size_t* workgroups, int* waves) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (slots) *slots = p->pslots;
-    if (runs) *runs = p->n_ops;
-    if (workgroups) *workgroups = p->n_blocks + p->n_packs;
-    if (waves) *waves = p->waves;
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_forces(nbx_leaf_plan* p, const void* bodies, size_t stride_bytes, int law, double G, double* forces_out, float* kernel_ms) {
-    if (kernel_ms) *kernel_ms = 0.0f;
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
-    if ((!bodies || !forces_out) && p->n) return fail(NBX_ERR_INVALID, "null argument");
-    const size_t min_stride = (size_t)(2 * p->dim + 1) * sizeof(double);
-    if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
-        return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
-    if (int src = plan_needs_structure(p)) return src;
-    if (law == NBX_LAW_NEWTON) {   // one host pass over the masses about to be copied (no other law pays for it)
-        double mass_max = 0.0;
-        const char* const m0 = static_cast<const char*>(bodies) + 2 * (size_t)p->dim * sizeof(double);
-        for (size_t i = 0; i < p->n; ++i) {
-            double m;
-            std::memcpy(&m, m0 + i * stride_bytes, sizeof m);
-            m = std::fabs(m);
-            if (!(m <= mass_max)) mass_max = m;      // a NaN stays: refused below
-        }
-        if (int lrc = plan_check_law(p, law, mass_max)) return lrc;
-    }
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    const size_t bytes = p->n * stride_bytes;
-    if (bytes > p->raw_bytes) {
-        if (p->raw) { NBX_HIP_TRY(hipStreamSynchronize(s)); NBX_HIP_TRY(hipFree(p->raw)); p->raw = nullptr; p->raw_bytes = 0; }
-        NBX_HIP_TRY(hipMalloc((void**)&p->raw, bytes + 256));
-        p->raw_bytes = bytes;
-    }
-    if (bytes) NBX_HIP_TRY(hipMemcpyAsync(p->raw, bodies, bytes, hipMemcpyHostToDevice, s));
-    NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
-    if (p->pslots) {
-        hipLaunchKernelGGL(leaf_gather_kernel, dim3((unsigned)((p->pslots + 255) / 256)), dim3(256), 0, s, p->raw, stride_bytes / sizeof(double), p->dim,
-                           p->pslot_body, (uint32_t)p->pslots, reinterpret_cast<float*>(p->xp), p->max_mass);
-        NBX_HIP_TRY(hipGetLastError());
-    }
-    if ((rc = plan_launch_pairs(p, law, s, true))) return rc;
-    p->evaluated = true; p->last_law = law;
-    p->last_signedG = (law == NBX_LAW_BRUTE) ? -G : G;   // brute force: forces[i] -= f (methods.cpp:131); tree codes: += (attractive)
-    p->last_mass = p->raw + 2 * p->dim; p->last_mass_stride = stride_bytes / sizeof(double); p->last_ctx_id = 0;
-    if ((rc = plan_mark_done(p, s))) return rc;
-    if ((rc = plan_forces_out(p, s, forces_out))) return rc;
-    if (kernel_ms && (p->n_blocks || p->n_packs)) NBX_HIP_TRY(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return NBX_OK;
-}
-
-// positions and masses of a context's resident bodies -> the plan's leaf-ordered source pairs, on stream s.  One lane per body
-// (coalesced reads, four 4-byte stores into its slot's pair record): 0.048 ms at N = 2^20.  A two-kernel form (SoA -> one float4 per
-// body, then one lane per slot reading its body's 16 bytes and writing whole records) was measured at 0.006 + 0.044 ms: no better.
-// What had made this gather 0.14-0.17 ms was not its memory traffic but publish_max_mass's predecessor (tools/ubench_gather.hip:
-// the traffic alone is 0.02 ms back to back).
-static int plan_gather_resident(nbx_leaf_plan* p, nbx_ctx* c, hipStream_t s) {
-    if (!p->pslots || !p->n) return NBX_OK;
-    hipLaunchKernelGGL(leaf_gather_by_body_kernel, dim3((unsigned)((p->n + 255) / 256)), dim3(256), 0, s, c->pos_all, c->mass_all, c->pad, p->dim,
-                       p->body_slot, p->n, reinterpret_cast<float*>(p->xp), p->max_mass);
-    NBX_HIP_TRY(hipGetLastError());
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_forces_ctx(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double* forces_out, float* kernel_ms) {
-    if (kernel_ms) *kernel_ms = 0.0f;
-    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
-    if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
-        return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
-    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
-    if (int src = plan_needs_structure(p)) return src;
-    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
-    if ((rc = plan_gather_resident(p, c, s))) return rc;
-    if ((rc = plan_launch_pairs(p, law, s, kernel_ms != nullptr))) return rc;
-    p->evaluated = true; p->last_law = law;
-    p->last_signedG = (law == NBX_LAW_BRUTE) ? -G : G;
-    p->last_mass = c->m64; p->last_mass_stride = 1; p->last_ctx_id = c->id;
-    if ((rc = plan_mark_done(p, s))) return rc;
-    if (forces_out) { if ((rc = plan_forces_out(p, s, forces_out))) return rc; }
-    else if (kernel_ms) NBX_HIP_TRY(hipStreamSynchronize(s));
-    if (kernel_ms && (p->n_blocks || p->n_packs)) NBX_HIP_TRY(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_get_forces(nbx_leaf_plan* p, double* forces_out) {
-    if (!p || (!forces_out && p->n)) return fail(NBX_ERR_INVALID, "null argument");
-    if (!p->evaluated) return fail(NBX_ERR_STATE, "no evaluation on the device");
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    // on the plan's own stream, behind the last evaluation's event (the stream that evaluation ran on may belong to a context that no longer exists)
-    if ((rc = plan_order_after_last(p, p->stream))) return rc;
-    if ((rc = plan_forces_out(p, p->stream, forces_out))) return rc;
-    return plan_mark_done(p, p->stream);
-}
-
-int nbx_leaf_plan_kick_drift(nbx_leaf_plan* p, nbx_ctx* c, double dt) {
-    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (!p->evaluated) return fail(NBX_ERR_STATE, "evaluate the leaf sums before kick_drift");
-    if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
-        return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
-    if (p->last_ctx_id != c->id) return fail(NBX_ERR_STATE, "the last evaluation was not made from this context");
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    SlotKickArgs k;
-    k.sums = p->sums; k.body_slot = p->body_slot; k.pslots = (uint32_t)p->pslots; k.dim = p->dim; k.pad = c->pad; k.count = c->count;
-    k.signedG = p->last_signedG; k.dt = dt; k.x64 = c->x64; k.v64 = c->v64; k.m64 = c->m64; k.pos_chunk = c->pos_all;
-    NBX_HIP_TRY(launch_kick_drift_slots(k, s));
-    c->have_accel = false;                          // the context's own accelerations (if any) belong to the old positions
-    c->tgt_cand_valid = 0; c->bad_list_pass = -1;
-    return plan_mark_done(p, s);
-}
-
-// one step's device work on stream s, nothing else (no events, no waits)
-static int plan_enqueue_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double signedG, double dt, hipStream_t s) {
-    NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
-    if (int rc = plan_gather_resident(p, c, s)) return rc;
-    if (int rc = plan_launch_pairs(p, law, s, false)) return rc;
-    SlotKickArgs k;
-    k.sums = p->sums; k.body_slot = p->body_slot; k.pslots = (uint32_t)p->pslots; k.dim = p->dim; k.pad = c->pad; k.count = c->count;
-    k.signedG = signedG; k.dt = dt; k.x64 = c->x64; k.v64 = c->v64; k.m64 = c->m64; k.pos_chunk = c->pos_all;
-    NBX_HIP_TRY(launch_kick_drift_slots(k, s));
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps) {
-    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
-    if (nsteps < 0) return fail(NBX_ERR_INVALID, "nsteps must be >= 0");
-    if (c->device != p->device || c->dim != p->dim || c->n_total != p->n || c->n_shards != 1)
-        return fail(NBX_ERR_INVALID, "the context must be a single-shard context of the plan's device, dimension and body count");
-    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies to the context first");
-    if (nsteps == 0) return NBX_OK;
-    if (int src = plan_needs_structure(p)) return src;
-    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    const double signedG = (law == NBX_LAW_BRUTE) ? -G : G;
-    // Plain launches, queued ahead of the device: a step is GPU-bound (0.36 ms of kernels at N = 2^20; 5 launches cost the host
-    // ~25 us).  A captured HIP graph was measured: 8-15 ms to capture and instantiate, then the same 72.4 ms per 200 steps at
-    // N = 2^20 and 7.97 against 8.39 ms at N = 20,000 -- it would need thousands of steps to pay for itself (tools/time_leaf_steps.py).
-    for (int k = 0; k < nsteps; ++k)
-        if ((rc = plan_enqueue_step(p, c, law, signedG, dt, s))) return rc;
-    p->evaluated = true; p->last_law = law;
-    p->last_signedG = signedG;
-    p->last_mass = c->m64; p->last_mass_stride = 1; p->last_ctx_id = c->id;
-    c->have_accel = false;                          // the context's own accelerations (if any) belong to the old positions
-    c->tgt_cand_valid = 0; c->bad_list_pass = -1;
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_step_octree(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
-    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
-    if (nsteps < 0 || rebuild_every < 0) return fail(NBX_ERR_INVALID, "nsteps and rebuild_every must be >= 0");
-    if (int rc = plan_check_ctx(p, c)) return rc;
-    if (rebuild_every > 0 && !p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
-    if (nsteps == 0) return NBX_OK;
-    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    const double signedG = (law == NBX_LAW_BRUTE) ? -G : G;
-    for (int k = 0; k < nsteps; ++k) {
-        if (rebuild_every > 0 && k % rebuild_every == 0 && (rc = plan_build_octree(p, c))) return rc;
-        if ((rc = plan_needs_structure(p))) return rc;
-        if ((rc = plan_enqueue_step(p, c, law, signedG, dt, s))) return rc;
-        p->evaluated = true; p->last_law = law;
-        p->last_signedG = signedG;
-        p->last_mass = c->m64; p->last_mass_stride = 1; p->last_ctx_id = c->id;
-        c->have_accel = false;                      // as nbx_leaf_plan_step
-        c->tgt_cand_valid = 0; c->bad_list_pass = -1;
-        if ((rc = plan_mark_done(p, s))) return rc;
-    }
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_set_cells(nbx_leaf_plan* p, const uint32_t* cell_first_leaf, const uint32_t* cell_leaf_count, size_t n_cells,
-                            const uint32_t* far_offsets, const uint32_t* far_cells) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (int src = plan_needs_structure(p)) return src;
-    // every index the two passes will follow, before anything is launched; a refused call leaves the plan and its cells as they were
-    if (const char* why = nbx_far::validate_cells(p->n_leaves, cell_first_leaf, cell_leaf_count, n_cells, far_offsets, far_cells))
-        return fail(NBX_ERR_INVALID, why);
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;   // the plan's own stream, behind the last evaluation wherever that was queued
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    if (!n_cells) {
-        NBX_HIP_TRY(hipStreamSynchronize(s));
-        plan_release_cells(p, true, false);
-        return plan_mark_done(p, s);
-    }
-    nbx_far::FarPlan fp;
-    std::vector<uint32_t> read_back;
-    const uint32_t* unit = p->unit_host.data();
-    if (p->unit_host.size() != p->n_leaves + 1) {      // laid out on the device: the array comes back once per set_cells (4 B per leaf)
-        try { read_back.assign(p->n_leaves + 1, 0u); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
-        if (p->n_leaves) {
-            NBX_HIP_TRY(hipMemcpyAsync(read_back.data(), p->unit_off, (p->n_leaves + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            NBX_HIP_TRY(hipStreamSynchronize(s));
-        }
-        unit = read_back.data();
-    }
-    try { nbx_far::plan_far(unit, p->n_leaves, cell_leaf_count, n_cells, far_offsets, fp); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
-    const size_t dim = (size_t)p->dim;
-    const size_t sizes[10] = {n_cells * 4, n_cells * 4, fp.small_cells.size() * 4, fp.big_cells.size() * 4, fp.far_entries * 4,
-                              fp.blocks.size() * sizeof(nbx_far::FarBlock), p->n_leaves * 4 * sizeof(double), n_cells * sizeof(double),
-                              n_cells * dim * sizeof(double), n_cells * sizeof(float4)};
-    size_t offs[10], total = 0;
-    for (int i = 0; i < 10; ++i) { offs[i] = total; total += (sizes[i] + 255) / 256 * 256 + 256; }
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
-    NBX_HIP_TRY(take_arena(p->device, total, &arena, &arena_bytes));
-    hipError_t e = hipSuccess;
-    for (hipEvent_t* ev : {&p->evm0, &p->evm1, &p->evf0, &p->evf1})
-        if (!*ev && e == hipSuccess) e = hipEventCreate(ev);
-    const void* const src[6] = {cell_first_leaf, cell_leaf_count, fp.small_cells.data(), fp.big_cells.data(), far_cells, fp.blocks.data()};
-    for (int i = 0; i < 6 && e == hipSuccess; ++i)
-        if (sizes[i]) e = hipMemcpyAsync(arena + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // the caller's arrays and the layout's are copied; the last evaluation is over too
-    if (e != hipSuccess) {
-        (void)hipFree(arena);
-        return nbx::fail_hip(e, "uploading the cells", __FILE__, __LINE__);
-    }
-    plan_release_cells(p, true, false);                 // the previous cells, if any: nothing on the device uses them any more
-    p->cell_arena = arena;
-    p->cell_arena_bytes = arena_bytes;
-    nbx_far::FarDevice& d = p->far;
-    d.xp = p->xp; d.unit_off = p->unit_off; d.sums = p->sums;
-    d.pslots = (uint32_t)p->pslots; d.n_leaves = (uint32_t)p->n_leaves; d.n_cells = (uint32_t)n_cells;
-    d.n_small = (uint32_t)fp.small_cells.size(); d.n_big = (uint32_t)fp.big_cells.size(); d.n_blocks = (uint32_t)fp.blocks.size();
-    d.cell_first = reinterpret_cast<uint32_t*>(arena + offs[0]);
-    d.cell_count = reinterpret_cast<uint32_t*>(arena + offs[1]);
-    d.small_cells = reinterpret_cast<uint32_t*>(arena + offs[2]);
-    d.big_cells = reinterpret_cast<uint32_t*>(arena + offs[3]);
-    d.far_cells = reinterpret_cast<uint32_t*>(arena + offs[4]);
-    d.blocks = reinterpret_cast<nbx_far::FarBlock*>(arena + offs[5]);
-    d.leaf_mom = reinterpret_cast<double*>(arena + offs[6]);
-    d.cell_mass = reinterpret_cast<double*>(arena + offs[7]);
-    d.cell_com = reinterpret_cast<double*>(arena + offs[8]);
-    d.cell_rec = reinterpret_cast<float4*>(arena + offs[9]);
-    p->far_entries = fp.far_entries;
-    if ((rc = plan_fit_quads(p))) { plan_release_cells(p, true, false); return rc; }   // the plan's order holds for the new cells
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_set_far_order(nbx_leaf_plan* p, int order) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (order != NBX_FAR_MONOPOLE && order != NBX_FAR_QUADRUPOLE) return fail(NBX_ERR_INVALID, "order must be NBX_FAR_MONOPOLE or NBX_FAR_QUADRUPOLE");
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    NBX_HIP_TRY(hipStreamSynchronize(s));               // the last evaluation is over: nothing reads the cells' records any more
-    if (order == p->far_order) return plan_mark_done(p, s);
-    const int before = p->far_order;
-    p->far_order = order;
-    if ((rc = plan_fit_quads(p))) { p->far_order = before; (void)plan_fit_quads(p); return rc; }
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_get_far_order(const nbx_leaf_plan* p, int* order) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (!order) return fail(NBX_ERR_INVALID, "order is null");
-    *order = p->far_order;
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_set_softening(nbx_leaf_plan* p, double epsilon) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (!(epsilon == 0.0 || (epsilon >= 1.0e-6 && epsilon <= 1.0e15))) return fail(NBX_ERR_INVALID, "softening must be 0 or in [1e-6, 1e15]");
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    NBX_HIP_TRY(hipStreamSynchronize(s));               // the last evaluation is over (its launches carry their own copy of eps^2 anyway)
-    p->softening = epsilon;
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_get_softening(const nbx_leaf_plan* p, double* epsilon) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (!epsilon) return fail(NBX_ERR_INVALID, "epsilon is null");
-    *epsilon = p->softening;
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_get_cell_quadrupoles(nbx_leaf_plan* p, double* q_out) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (p->far_order != NBX_FAR_QUADRUPOLE) return fail(NBX_ERR_STATE, "the plan's far order is NBX_FAR_MONOPOLE: no second moments are computed");
-    if (!p->far.n_cells) return NBX_OK;
-    if (!p->cells_evaluated || !p->quads_evaluated) return fail(NBX_ERR_STATE, "no evaluation at NBX_FAR_QUADRUPOLE since the cells were set");
-    if (!q_out) return fail(NBX_ERR_INVALID, "q_out is null");
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    NBX_HIP_TRY(hipMemcpyAsync(q_out, p->far.cell_quad, (size_t)p->far.n_cells * nbx_far::quad_count(p->dim) * sizeof(double), hipMemcpyDeviceToHost, s));
-    NBX_HIP_TRY(hipStreamSynchronize(s));
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_get_cells(nbx_leaf_plan* p, double* mass_out, double* com_out) {
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (!p->far.n_cells) return NBX_OK;
-    if (!p->cells_evaluated) return fail(NBX_ERR_STATE, "no evaluation since the cells were set");
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    const size_t nc = p->far.n_cells;
-    if (mass_out) NBX_HIP_TRY(hipMemcpyAsync(mass_out, p->far.cell_mass, nc * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (com_out) NBX_HIP_TRY(hipMemcpyAsync(com_out, p->far.cell_com, nc * (size_t)p->dim * sizeof(double), hipMemcpyDeviceToHost, s));
-    NBX_HIP_TRY(hipStreamSynchronize(s));
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_cell_info(nbx_leaf_plan* p, size_t* n_cells, size_t* far_entries, float* moments_ms, float* far_ms) {
-    if (moments_ms) *moments_ms = 0.0f;
-    if (far_ms) *far_ms = 0.0f;
-    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
-    if (n_cells) *n_cells = p->far.n_cells;
-    if (far_entries) *far_entries = p->far_entries;
-    if ((moments_ms || far_ms) && p->far.n_cells && p->cells_evaluated && p->cells_timed) {
-        DeviceScope scope;
-        int rc = plan_set_device(p);
-        if (rc) return rc;
-        NBX_HIP_TRY(hipEventSynchronize(p->evf1));
-        if (moments_ms) NBX_HIP_TRY(hipEventElapsedTime(moments_ms, p->evm0, p->evm1));
-        if (far_ms) NBX_HIP_TRY(hipEventElapsedTime(far_ms, p->evf0, p->evf1));
-    }
-    return NBX_OK;
-}
-
-int nbx_leaf_plan_time_kernel(nbx_leaf_plan* p, int law, int reps, float* mean_ms) {
-    if (!p || !mean_ms) return fail(NBX_ERR_INVALID, "null argument");
-    *mean_ms = 0.0f;
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
-    if (reps < 1 || reps > 1000) return fail(NBX_ERR_INVALID, "reps must be in [1, 1000]");
-    if (!p->evaluated) return fail(NBX_ERR_STATE, "evaluate once before timing (the bodies of the last evaluation are used)");
-    if (int lrc = plan_check_law(p, law, -1.0)) return lrc;      // the softening length; the masses below
-    DeviceScope scope;
-    int rc = plan_set_device(p);
-    if (rc) return rc;
-    hipStream_t s = p->stream;   // the plan's own stream, behind the last evaluation (see nbx_leaf_plan_get_forces)
-    if ((rc = plan_order_after_last(p, s))) return rc;
-    if (law == NBX_LAW_NEWTON) {   // the largest |mass| of the bodies the launches will read: the word the last gather left (fp32 bits)
-        float mass_max = 0.0f;
-        NBX_HIP_TRY(hipMemcpyAsync(&mass_max, p->max_mass, sizeof(float), hipMemcpyDeviceToHost, s));
-        NBX_HIP_TRY(hipStreamSynchronize(s));
-        if (int lrc = plan_check_law(p, law, (double)mass_max)) return lrc;
-    }
-    const int timed_from = reps / 2;
-    for (int r = 0; r < reps; ++r) {
-        if (r == timed_from) NBX_HIP_TRY(hipEventRecord(p->ev0, s));
-        if ((rc = plan_launch_near(p, law, s, false))) return rc;
-    }
-    NBX_HIP_TRY(hipEventRecord(p->ev1, s));
-    if (p->cells_evaluated && (rc = plan_launch_far(p, law, s, false, false))) return rc;   // the sums keep their far terms (the last evaluation's moments)
-    NBX_HIP_TRY(hipStreamSynchronize(s));
-    if (p->n_blocks || p->n_packs) NBX_HIP_TRY(hipEventElapsedTime(mean_ms, p->ev0, p->ev1));
-    *mean_ms /= (float)(reps - timed_from);
-    // the sums now belong to `law`: keep the bookkeeping of the last evaluation consistent with them
-    p->last_signedG = (law == NBX_LAW_BRUTE) ? -std::fabs(p->last_signedG) : std::fabs(p->last_signedG);
-    p->last_law = law;
-    return plan_mark_done(p, s);
-}
-
-}  // extern "C"
+}  // namespace nbx_near

@@ -1,4 +1,4 @@
-// leaf_plan.h -- host side of the leaf-pair path (csrc/leaf_pair_kernel.hip): everything the pair kernel follows, laid out once per
+// leaf_plan.h -- host side of the leaf-pair path (kernels: csrc/leaf_pair_kernel.hip; entry points: csrc/leaf_plan_api.hip): everything the pair kernel follows, laid out once per
 // call from the caller's CSR arrays.  Plain C++ (no HIP): tests/test_leaf_plan_cpu.py compiles it with g++ and checks its
 // invariants without a GPU.  The comment at the top of leaf_pair_kernel.hip says what each piece is for.
 #pragma once

@@ -4,6 +4,7 @@
 #include "../../include/nbody_hip.h"
 #include "nbx_internal.h"
 #include "nbx_ctx.h"
+#include "device_block.h"
 
 #include <algorithm>
 #include <atomic>
@@ -70,76 +71,41 @@ void park_stream(int device, hipStream_t s) {   // s is idle: the caller has syn
     (void)hipStreamDestroy(s);
 }
 
-// The same for a context's device allocation: hipFree of a few MB costs 0.2 ms on this runtime, hipMalloc not much less, and the
-// drop-in call makes and destroys a context per call -- at N = 1,000 that was half of the call.  A destroyed context parks its
-// arena (up to kArenaParkMaxBytes; two per device); the next context on that device that fits takes it.  Nothing in the library
-// relies on fresh memory being zero (hipMalloc does not promise it either).
+}  // namespace nbx
+
+// The parked-block pools of device_block.h over hipMalloc / hipFree: the leaf plans' and the contexts', each with its own mutex
+// (neither is ever held together with the other's or with the stream pool's).
+namespace nbx_block {
 namespace {
-struct ParkedCtxArena { int device; char* p; size_t bytes; };
-std::vector<ParkedCtxArena> g_ctx_arenas;   // under g_stream_pool_mu
-// 1 GiB: since the mixed mode became the default a context's block carries the fp64 pass's sums (8 x dim x pad doubles: 201 MB at
-// N = 2^20, 805 MB at 2^22), and a one-shot call per step at such sizes would otherwise hipMalloc and hipFree hundreds of MB each
-// time -- the cost the parking exists to avoid.  288 GB of HBM do not miss two idle blocks; nbx_release_cached() frees them.
-constexpr size_t kArenaParkMaxBytes = (size_t)1 << 30;
-constexpr size_t kArenasParkedPerDevice = 2;
-}  // namespace
-
-hipError_t take_ctx_arena(int device, size_t bytes, char** out, size_t* got) {
-    {
-        std::lock_guard<std::mutex> lock(g_stream_pool_mu);
-        size_t best = g_ctx_arenas.size();
-        for (size_t i = 0; i < g_ctx_arenas.size(); ++i)
-            if (g_ctx_arenas[i].device == device && g_ctx_arenas[i].bytes >= bytes && g_ctx_arenas[i].bytes <= 4 * bytes + (1u << 20) &&
-                (best == g_ctx_arenas.size() || g_ctx_arenas[i].bytes < g_ctx_arenas[best].bytes)) best = i;
-        if (best != g_ctx_arenas.size()) {
-            *out = g_ctx_arenas[best].p;
-            *got = g_ctx_arenas[best].bytes;
-            g_ctx_arenas.erase(g_ctx_arenas.begin() + (long)best);
-            return hipSuccess;
-        }
-    }
-    *got = bytes;
+int hip_alloc(int /*device: the caller's current one*/, size_t bytes, char** out) {
     void* a = nullptr;
-    hipError_t e = hipMalloc(&a, bytes);
-    if (e == hipErrorOutOfMemory) {   // parked allocations (here and in the leaf path) may be what is in the way
-        (void)hipGetLastError();
-        release_parked_ctx_arenas();
-        release_parked_leaf_arenas();
-        e = hipMalloc(&a, bytes);
-    }
+    const hipError_t e = hipMalloc(&a, bytes);
+    if (e != hipSuccess) (void)hipGetLastError();
     *out = static_cast<char*>(a);
-    return e;
+    return (int)e;
 }
-
-void park_ctx_arena(int device, char* p, size_t bytes) {   // nothing on the device uses p any more
-    char* evicted = nullptr;
-    if (bytes <= kArenaParkMaxBytes) {
-        std::lock_guard<std::mutex> lock(g_stream_pool_mu);
-        g_ctx_arenas.push_back(ParkedCtxArena{device, p, bytes});
-        size_t mine = 0, oldest = g_ctx_arenas.size();
-        for (size_t i = 0; i < g_ctx_arenas.size(); ++i)
-            if (g_ctx_arenas[i].device == device) { if (oldest == g_ctx_arenas.size()) oldest = i; ++mine; }
-        if (mine > kArenasParkedPerDevice) { evicted = g_ctx_arenas[oldest].p; g_ctx_arenas.erase(g_ctx_arenas.begin() + (long)oldest); }
+void hip_free(int device, char* p) {
+    int current = device;
+    if (hipGetDevice(&current) == hipSuccess && current != device) {   // release_all on a process that uses several devices
+        if (hipSetDevice(device) == hipSuccess) (void)hipFree(p);
+        (void)hipSetDevice(current);
     } else {
-        evicted = p;
+        (void)hipFree(p);
     }
-    if (evicted) (void)hipFree(evicted);
 }
-
-void release_parked_ctx_arenas() {
-    std::vector<ParkedCtxArena> parked;
-    {
-        std::lock_guard<std::mutex> lock(g_stream_pool_mu);
-        parked.swap(g_ctx_arenas);
-    }
-    int before = 0;
-    const bool have = hipGetDevice(&before) == hipSuccess;
-    for (auto& e : parked)
-        if (hipSetDevice(e.device) == hipSuccess) (void)hipFree(e.p);
-    if (have) (void)hipSetDevice(before);
+void release_all_pools() {
+    ctx_pool().release_all();
+    leaf_pool().release_all();
     (void)hipGetLastError();
 }
+const Backend kHipBackend = {hip_alloc, hip_free, release_all_pools, (int)hipErrorOutOfMemory};
+}  // namespace
+const Backend& hip_backend() { return kHipBackend; }
+Pool& leaf_pool() { static Pool pool(kLeafPolicy, kHipBackend); return pool; }
+Pool& ctx_pool() { static Pool pool(kCtxPolicy, kHipBackend); return pool; }
+}  // namespace nbx_block
 
+namespace nbx {
 // the ids of the live contexts (a plan's last evaluation names its context by id: the arena of a destroyed context is parked and
 // handed to the next one, so an address says nothing)
 namespace {
@@ -223,17 +189,10 @@ int dev_alloc(nbx_ctx* c, T** p, size_t bytes) {
         c->arena_used += bytes;
         return NBX_OK;
     }
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e == hipErrorOutOfMemory) {   // parked allocations (the leaf path's: up to 2 x 2 GiB per device; destroyed contexts') may be what is in the way
-        (void)hipGetLastError();
-        release_parked_leaf_arenas();
-        release_parked_ctx_arenas();
-        e = hipMalloc(&q, bytes);
-    }
-    HIP_TRY(e);
+    char* q = nullptr;   // out of memory: parked blocks (the leaf path's: up to 2 x 2 GiB per device; destroyed contexts') may be what is in the way
+    HIP_TRY((hipError_t)nbx_block::alloc_retry(nbx_block::hip_backend(), c->device, bytes, &q));
     c->extra.push_back(q);
-    *p = static_cast<T*>(q);
+    *p = reinterpret_cast<T*>(q);
     return NBX_OK;
 }
 
@@ -623,8 +582,7 @@ double nbx_refine_sigma_default(int dim) { return dim == 2 ? kRefineSigmaDefault
 
 int nbx_release_cached(void) {
     release_parked_communicators();
-    release_parked_leaf_arenas();
-    release_parked_ctx_arenas();
+    nbx_block::hip_backend().release_all_pools();
     release_parked_streams();
     return NBX_OK;
 }
@@ -709,7 +667,7 @@ int nbx_ctx_create(nbx_ctx** out, int device, int dim, size_t n_total, int n_sha
             want += arena_round((size_t)splits * variant_planes(c->variant) * pad * sizeof(float)) + arena_round(list_bytes) + arena_round(acc_bytes);
         }
         if (want <= ((size_t)64 << 30)) {   // beyond that the pieces are allocated one by one, and fail one by one
-            CTX_TRY(take_ctx_arena(device, want, &c->arena, &c->arena_bytes));   // a parked one of a destroyed context, or a fresh one
+            CTX_TRY((hipError_t)nbx_block::ctx_pool().take(device, want, &c->arena, &c->arena_bytes));   // a parked one of a destroyed context, or a fresh one
         }
     }
 #define CTX_ALLOC(ptr, bytes) do { int r_ = dev_alloc(c, &(ptr), (bytes)); if (r_) { nbx_ctx_destroy(c); return r_; } } while (0)
@@ -734,7 +692,7 @@ int nbx_ctx_destroy(nbx_ctx* c) {
     for (void* p : c->extra) (void)hipFree(p);   // every device buffer is a piece of the arena or one of these
     if (c->arena) {   // the stream(s) were synchronised above: nothing on the device uses it any more
         const bool idle = (!c->stream || hipStreamSynchronize(c->stream) == hipSuccess) && (!c->own_stream || hipStreamSynchronize(c->own_stream) == hipSuccess);
-        if (idle) park_ctx_arena(c->device, c->arena, c->arena_bytes);
+        if (idle) nbx_block::ctx_pool().park(c->device, c->arena, c->arena_bytes);
         else (void)hipFree(c->arena);
     }
     if (c->counters_host) (void)hipHostFree(c->counters_host);

@@ -115,10 +115,7 @@ int fail(int code, const char* msg);
 hipError_t take_stream(int device, hipStream_t* out);
 void park_stream(int device, hipStream_t s);
 void release_parked_streams();
-// a destroyed context's device allocation is kept for the next context on that device (nbx_api.hip)
-hipError_t take_ctx_arena(int device, size_t bytes, char** out, size_t* got);
-void park_ctx_arena(int device, char* p, size_t bytes);
-void release_parked_ctx_arenas();
+// (a destroyed context's device allocation is kept for the next context on that device: device_block.h's ctx_pool)
 // the two halves of nbx_ctx_upload_bodies (nbx_api.hip), apart so that the node layer can upload each rank's own shard
 // only and fill the other chunks device to device in between
 int upload_stage(nbx_ctx* c, const void* bodies, size_t stride_bytes, bool only_own, unsigned long long facts[3],
@@ -126,7 +123,6 @@ int upload_stage(nbx_ctx* c, const void* bodies, size_t stride_bytes, bool only_
 int upload_finish(nbx_ctx* c, const unsigned long long facts[3]);
 bool ctx_alive(unsigned long long id);  // nbx_api.hip: a context with this id exists (created, not yet destroyed)
 void release_parked_communicators();   // nbx_node.hip
-void release_parked_leaf_arenas();     // leaf_pair_kernel.hip
 }  // namespace nbx
 
 #define NBX_HIP_TRY(expr)                                                           \

@@ -252,7 +252,7 @@ struct KickDriftArgs {
     float* pos_chunk;      // this shard's chunk of pos_all: [dim][pad]
 };
 hipError_t launch_kick_drift(const KickDriftArgs& k, hipStream_t stream);
-// The same update from fp64 leaf sums indexed by padded slot (leaf plan, leaf_pair_kernel.hip): body l's sum is
+// The same update from fp64 leaf sums indexed by padded slot (leaf plan, leaf_plan_api.hip): body l's sum is
 // sums[k][body_slot[l]] (0 when body_slot[l] == 0xffffffff: the body belongs to no leaf); F = (signedG m) sum.
 struct SlotKickArgs {
     const double* sums;        // [dim][pslots]

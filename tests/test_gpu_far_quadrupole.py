@@ -390,6 +390,43 @@ def test_stepping_at_order_1(nbx, oracle):
             assert np.array_equal(plan.forces_ctx(c, law, G), want)
 
 
+def _cell_subset(cells, far, keep):
+    """The cells with keep[c] set, renumbered, and the far lists with the others' entries dropped."""
+    u32 = lambda a: np.asarray(a, dtype=np.uint32)
+    fo, fc = np.asarray(far[0], dtype=np.int64), np.asarray(far[1], dtype=np.int64)
+    owner = np.repeat(np.arange(fo.size - 1), np.diff(fo))
+    kept = keep[fc]
+    fo2 = np.concatenate([[0], np.cumsum(np.bincount(owner[kept], minlength=fo.size - 1))])
+    return (u32(np.asarray(cells[0])[keep]), u32(np.asarray(cells[1])[keep])), (u32(fo2), u32((np.cumsum(keep) - 1)[fc[kept]]))
+
+
+def test_cell_and_moment_blocks_are_refitted(nbx, oracle):
+    """One plan whose cells are replaced by a larger set and then by a smaller one, the far order switched to 1 and back between the
+    evaluations: the cells' block and the second moments' block are outgrown, given back and taken again, then kept while they fit
+    (csrc/device_block.h Block::fit).  Every evaluation equals a fresh plan's with those cells at that order, bit for bit."""
+    n, dim, law, G = 3000, 3, nbx.LAW_TREE_LEAF, oracle.G
+    b = oracle.round_inputs_to_f32(oracle.generate(57, n, dim))
+    leaves, cells, far = octree(nbx, b, dim, 3, 0.7)
+    idx = np.arange(np.asarray(cells[0]).size)
+    third, half = _cell_subset(cells, far, idx % 3 == 0), _cell_subset(cells, far, idx % 2 == 0)
+    assert third[0][0].size < half[0][0].size < idx.size and third[1][1].size < half[1][1].size < np.asarray(far[1]).size
+    seen = {}
+    with nbx.LeafPlan(n, dim, *leaves) as plan:
+        for what, (c, f), orders in (("a third", third, (0, 1)), ("all (larger)", (cells, far), (1, 0, 1)), ("half (smaller)", half, (1, 0, 1, 0))):
+            plan.set_cells(*c, *f)
+            for k, order in enumerate(orders):
+                plan.set_far_order(order)
+                got = plan.forces(b, law, G)
+                if (what, order) not in seen:
+                    with nbx.LeafPlan(n, dim, *leaves) as fresh:
+                        fresh.set_far_order(order)
+                        fresh.set_cells(*c, *f)
+                        seen[what, order] = fresh.forces(b, law, G)
+                assert np.array_equal(got, seen[what, order]), f"{what} of the cells, evaluation {k} at order {order}"
+            assert not np.array_equal(seen[what, 0], seen[what, 1]), f"{what}: order 1 must change the forces, or the test shows nothing"
+    assert not np.array_equal(seen["a third", 0], seen["all (larger)", 0]) and not np.array_equal(seen["half (smaller)", 0], seen["all (larger)", 0])
+
+
 def test_accuracy_on_the_device(nbx, oracle):
     """N = 32,768 generated bodies, depth 4, theta 0.5, 4,096 sampled rows against the oracle's all-pairs sums: the median and the
     99th percentile of the relative error at order 1 are at least MIN_GAIN (test_far_quadrupole_cpu.py) times below order 0's.  A

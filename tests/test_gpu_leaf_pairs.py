@@ -1,4 +1,4 @@
-"""GPU: SURVEY 8(f-4) -- nbx_leaf_pair_forces (csrc/leaf_pair_kernel.hip, through the C ABI) against the oracle's
+"""GPU: SURVEY 8(f-4) -- nbx_leaf_pair_forces (csrc/leaf_plan_api.hip and the kernels of csrc/leaf_pair_kernel.hip, through the C ABI) against the oracle's
 restatement of the reference's leaf direct sums (fmm_parlay.cpp:992-1020, bvh.cpp:150-176, octree.cpp:105-125) and
 against the committed outputs of the reference's own octree walked with theta = 0.  Same stated fp32 tolerance as the
 brute-force path (oracle_lib.TOL_*)."""

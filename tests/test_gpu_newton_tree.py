@@ -1,4 +1,4 @@
-"""GPU: softened Newtonian gravity on a leaf plan (NBX_LAW_NEWTON with nbx_leaf_plan_set_softening; csrc/leaf_pair_kernel.hip,
+"""GPU: softened Newtonian gravity on a leaf plan (NBX_LAW_NEWTON with nbx_leaf_plan_set_softening; csrc/leaf_plan_api.hip, csrc/leaf_pair_kernel.hip,
 csrc/leaf_far_kernel.hip) through the C ABI.
 
 References.  The near field on complete structures is judged against the project's all-pairs checker of the context's Newtonian law,

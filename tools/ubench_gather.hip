@@ -1,4 +1,4 @@
-// Micro-benchmark behind the resident gather of the leaf-pair path (csrc/leaf_pair_kernel.hip): 2^20 bodies as float4 {x,y,z,m} in
+// Micro-benchmark behind the resident gather of the leaf-pair path (leaf_gather_by_body_kernel, csrc/leaf_pair_kernel.hip; plan_gather_resident, csrc/leaf_plan_api.hip): 2^20 bodies as float4 {x,y,z,m} in
 // body order -> leaf-ordered source pairs {xa,xb,ya,yb},{za,zb,ma,mb} through a random permutation.  Which side costs what?
 //   hipcc --offload-arch=gfx950 -O3 tools/ubench_gather.hip -o /tmp/ubench_gather && /tmp/ubench_gather
 #include <hip/hip_runtime.h>
