@@ -22,7 +22,7 @@ all: lib oracle nbody_sim
 lib: $(LIB)
 
 OBJS := $(addprefix $(CSRC)/,$(addsuffix $(O),force_kernel force_sym_kernel force_launch state_kernels nbx_api nbx_node leaf_pair_kernel \
-          leaf_plan_api leaf_far_kernel octree_device close_hash measure_kernels))
+          leaf_plan_api leaf_far_kernel leaf_phi_kernel octree_device close_hash measure_kernels))
 # name of the force-kernel variant used when the caller does not pick one
 # (round 4: the three-level summation build -- same pair arithmetic, fp32 errors ~3x smaller for +1.5 % time)
 DEFAULT_VARIANT ?= fastpk3l_t8_w3_u4
@@ -64,11 +64,15 @@ $(CSRC)/leaf_pair_kernel$(O): $(CSRC)/leaf_pair_kernel.hip $(CSRC)/leaf_near.h $
 	$(HIPCC) $(HIPFLAGS) $(LEAF_DEFS) -c $< -o $@
 
 # ... and the host side behind the C ABI: the one-shot call and nbx_leaf_plan_* (with the device planner's kernels, leaf_plan_device.h)
-$(CSRC)/leaf_plan_api$(O): $(CSRC)/leaf_plan_api.hip $(CSRC)/leaf_near.h $(CSRC)/leaf_plan.h $(CSRC)/leaf_plan_device.h $(CSRC)/leaf_far.h $(CSRC)/octree_device.h $(CSRC)/device_sort.h $(CSRC)/device_block.h $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
+$(CSRC)/leaf_plan_api$(O): $(CSRC)/leaf_plan_api.hip $(CSRC)/leaf_near.h $(CSRC)/leaf_plan.h $(CSRC)/leaf_plan_device.h $(CSRC)/leaf_far.h $(CSRC)/leaf_phi.h $(CSRC)/octree_device.h $(CSRC)/device_sort.h $(CSRC)/device_block.h $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) $(LEAF_DEFS) -c $< -o $@
 
 # the far field of a leaf plan: moment and far kernels
 $(CSRC)/leaf_far_kernel$(O): $(CSRC)/leaf_far_kernel.hip $(CSRC)/leaf_far.h $(CSRC)/leaf_law.h $(CSRC)/nbx_internal.h include/nbody_hip.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the potential of a leaf plan: near, far and reduction kernels (the flags of the other leaf kernels)
+$(CSRC)/leaf_phi_kernel$(O): $(CSRC)/leaf_phi_kernel.hip $(CSRC)/leaf_phi.h $(CSRC)/leaf_far.h $(CSRC)/leaf_plan.h $(CSRC)/leaf_law.h $(CSRC)/nbx_internal.h include/nbody_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the octree built on the device.  -ffp-contract=off: a body's cell index must round like the host builder's two-step arithmetic

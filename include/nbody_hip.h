@@ -326,6 +326,43 @@ int nbx_leaf_plan_get_structure(nbx_leaf_plan* plan, uint32_t* leaf_offsets, uin
  * sums and the last structure built. */
 int nbx_leaf_plan_step_octree(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, double dt, int nsteps, int rebuild_every);
 
+/* ---- the potential through a plan -------------------------------------------------------------------------------------------
+ * What the plan's sums are the gradient of, through the same near lists and far cells, in O(list length) like the forces.  Per unit
+ * G m_i, body i of target leaf t has
+ *       phi_i = sum over bodies j != i of the leaves on t's near list of  m_j w(r_ij)
+ *             + sum over the cells c on t's far list of                   Phi_c(R),   R = com_c - p_i
+ * with the law's pair potential w:
+ *       NBX_LAW_NEWTON      w = 1 / rho, rho^2 = r^2 + epsilon^2; the body itself is left out by IDENTITY (its own slot), so two
+ *                           different bodies at one position count m_j / epsilon
+ *       NBX_LAW_BRUTE       w = 1 / (2 r^2); pairs with r^2 < 1e-10 are left out (the law's own skip)
+ *       NBX_LAW_TREE_LEAF   w = 1 / (2 r^2); pairs with r^2 < 1e-9 are left out
+ *       NBX_LAW_FMM_P2P     NBX_ERR_INVALID: its smoothed magnitude with unsmoothed direction below 1e-10 is no gradient
+ * A far cell with q = Q / M_c (the record the moment pass writes) and t = tr q adds, at NBX_FAR_MONOPOLE / NBX_FAR_QUADRUPOLE,
+ *       NEWTON      M_c / rho         (M_c / rho)     [ 1 - t / (2 rho^2) + (3/2) R^T q R / rho^4 ]
+ *       reference   M_c / (2 r^2)     (M_c / (2 r^2)) [ 1 - t / r^2       + 4     R^T q R / r^4   ]
+ * (0 where the law skips the pair with the pseudo-body; a massless cell adds 0; a cell whose q record is the all-zero fallback adds
+ * its monopole alone).  Totals: U = s (G / 2) sum_i m_i phi_i with s = +1 for NBX_LAW_BRUTE (on complete lists nbx_ctx_energy's
+ * potential) and -1 for the two others (NEWTON: -sum_{i<j} G m_i m_j / rho); K = sum_i m_i |v_i|^2 / 2 from the context's fp64 state.
+ * A body in no leaf has phi_i = 0 and still counts in K.  The terms are fp32 like every pair term, the sums fp64 in a fixed order.
+ *
+ * A potential call is an OBSERVER.  It leaves untouched the slot sums of the last force evaluation, that evaluation's law, sign and
+ * masses, and the context's bodies: nbx_leaf_plan_get_forces, _kick_drift, _step and _step_octree afterwards give the bits they would
+ * have given without it.  It does gather the source pairs again and recompute the cells' moments: nbx_leaf_plan_get_cells,
+ * _get_cell_quadrupoles and _time_kernel afterwards refer to the positions the potential call saw.  On a plan built on the device
+ * the structure is the one of the last (re)build; the call does not rebuild.  The far order and the softening length are the plan's.
+ * A plan never asked for a potential allocates nothing for it.  Every call synchronises.
+ * Refused before anything is launched: NBX_ERR_INVALID for a null plan / ctx / phi_out, an unknown law or NBX_LAW_FMM_P2P, a refused
+ * body stride, a context of the wrong device, dimension, body count or shard count, and max|m| / epsilon^3 outside fp32's normal
+ * range (nbx_leaf_plan_set_softening's rule); NBX_ERR_STATE for NBX_LAW_NEWTON while epsilon is 0, a context with nothing uploaded,
+ * and a plan whose last octree build was refused.  There is no CPU fallback. */
+/* host bodies in, per-body potentials out: phi_out[n_bodies], per unit G m_i; the twin of nbx_leaf_plan_forces */
+int nbx_leaf_plan_potentials(nbx_leaf_plan* plan, const void* bodies, size_t body_stride_bytes, int law, double* phi_out);
+/* resident bodies: the context's positions as they stand now, the moment pass (if the plan has cells), near + far potential,
+ * reduction.  Either out pointer may be NULL. */
+int nbx_leaf_plan_energy(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, double* kinetic, double* potential);
+/* phi of the last nbx_leaf_plan_energy / _potentials call, n_bodies doubles; NBX_ERR_STATE before the first */
+int nbx_leaf_plan_get_potentials(nbx_leaf_plan* plan, double* phi_out);
+
 /* ---- device-resident context ------------------------------------------------------------------
  * A context owns the targets of ONE shard of an N-body system on ONE device and a full-length
  * fp32 copy of all N sources.  n_shards = 1, shard = 0 is the single-GPU case.  With n_shards = G

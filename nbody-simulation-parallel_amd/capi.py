@@ -64,6 +64,9 @@ ABI = [
     ("nbx_leaf_plan_structure_sizes", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz)]),
     ("nbx_leaf_plan_get_structure", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("nbx_leaf_plan_step_octree", _i, [_vp, _vp, _i, _d, _d, _i, _i]),
+    ("nbx_leaf_plan_potentials", _i, [_vp, _vp, _sz, _i, _vp]),
+    ("nbx_leaf_plan_energy", _i, [_vp, _vp, _i, _d, _pd, _pd]),
+    ("nbx_leaf_plan_get_potentials", _i, [_vp, _vp]),
     ("nbx_ctx_create", _i, [_c.POINTER(_vp), _i, _i, _sz, _i, _i]),
     ("nbx_ctx_destroy", _i, [_vp]),
     ("nbx_ctx_set_stream", _i, [_vp, _vp]),
@@ -473,6 +476,28 @@ class LeafPlan:
         ms = ctypes.c_float(0.0)
         self._ck(self.lib.nbx_leaf_plan_time_kernel(self.h, law, reps, ctypes.byref(ms)), "nbx_leaf_plan_time_kernel")
         return ms.value
+
+    def potentials(self, bodies: np.ndarray, law: int) -> np.ndarray:
+        """Host bodies in, per-body potentials out, per unit G m_i (nbx_leaf_plan_potentials): the law's pair potential summed over
+        the near lists and the far cells at the plan's order and softening.  An observer: the last force evaluation stays as it is."""
+        b, dim = _as_bodies(bodies)
+        if dim != self.dim or b.shape[0] != self.n:
+            raise ValueError("bodies shape does not match the plan")
+        out = np.empty(self.n, dtype=np.float64)
+        self._ck(self.lib.nbx_leaf_plan_potentials(self.h, b.ctypes.data, b.shape[1] * 8, int(law), out.ctypes.data), "nbx_leaf_plan_potentials")
+        return out
+
+    def energy(self, ctx: "Context", law: int, G: float = REFERENCE_G):
+        """(kinetic, potential) of the bodies resident in `ctx`, the potential through the plan's lists (nbx_leaf_plan_energy)."""
+        ke, pe = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._ck(self.lib.nbx_leaf_plan_energy(self.h, ctx.h, int(law), float(G), ctypes.byref(ke), ctypes.byref(pe)), "nbx_leaf_plan_energy")
+        return ke.value, pe.value
+
+    def get_potentials(self) -> np.ndarray:
+        """phi[n] of the last energy / potentials call (nbx_leaf_plan_get_potentials)."""
+        out = np.empty(self.n, dtype=np.float64)
+        self._ck(self.lib.nbx_leaf_plan_get_potentials(self.h, out.ctypes.data), "nbx_leaf_plan_get_potentials")
+        return out
 
 
 class Context:

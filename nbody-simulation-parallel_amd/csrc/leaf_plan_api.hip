@@ -1,13 +1,15 @@
 // leaf_plan_api.hip -- the host side of the leaf-pair path behind the C ABI (include/nbody_hip.h): the one-shot call
 // nbx_leaf_pair_forces and the device-resident plan nbx_leaf_plan_*.  Validation, the choice of planner (leaf_plan.h on the host,
 // leaf_plan_device.h on the device), the octree built on the device (octree_device.h), and every entry point.  The kernels are
-// leaf_pair_kernel.hip's (through leaf_near.h) and leaf_far_kernel.hip's (leaf_far.h); device memory is device_block.h's.
+// leaf_pair_kernel.hip's (through leaf_near.h), leaf_far_kernel.hip's (leaf_far.h) and, for the potential, leaf_phi_kernel.hip's
+// (leaf_phi.h); device memory is device_block.h's.
 #include "../../include/nbody_hip.h"
 #include "nbx_ctx.h"
 #include "device_block.h"
 #include "leaf_plan.h"
 #include "leaf_near.h"
 #include "leaf_far.h"
+#include "leaf_phi.h"
 #include "leaf_plan_device.h"
 #include "octree_device.h"
 
@@ -116,6 +118,13 @@ struct nbx_leaf_plan {
     nbx_octree::Tree tree;
     nbx_octree::Counts counts_host{};     // the builder's 64 bytes land here
     const uint32_t* list_sources_dev = nullptr;   // in the arena
+    // ---- the potential (nbx_leaf_plan_energy / _potentials; leaf_phi.h): nothing below exists until a caller first asks for one ----
+    Block phi_block;                // phi by slot | phi by body | the reduction's partials; fitted by every potential call
+    double* phi_slot = nullptr;     // [pslots] per unit G m_i, without the reference laws' factor 1/2
+    double* phi_body = nullptr;     // [n] what nbx_leaf_plan_get_potentials hands out
+    double* phi_part = nullptr;     // [2][ceil(n / 256)]
+    bool phi_valid = false;         // a potential call has gone through
+    Block phi_raw;                  // staged Body<D> array of nbx_leaf_plan_potentials -- not `raw`: the masses of the last force evaluation may live there
 };
 
 namespace {
@@ -790,6 +799,8 @@ int nbx_leaf_plan_destroy(nbx_leaf_plan* p) {
     p->tree_arena.release(all_idle);
     p->forces_own.release(all_idle);
     p->raw.release(all_idle);
+    p->phi_block.release(all_idle);
+    p->phi_raw.release(all_idle);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     if (p->done) (void)hipEventDestroy(p->done);
@@ -1137,6 +1148,123 @@ int nbx_leaf_plan_time_kernel(nbx_leaf_plan* p, int law, int reps, float* mean_m
     p->last_signedG = signed_G(law, std::fabs(p->last_signedG));
     p->last_law = law;
     return plan_mark_done(p, s);
+}
+
+// ---- the potential (leaf_phi.h) -------------------------------------------------------------------------------------------------
+// A potential call is an OBSERVER: it writes the plan's source pairs, the largest-mass word and the cells' moments (which every
+// evaluation writes afresh), the plan's phi block, and nothing else -- not the slot sums, not the record of the last evaluation.
+static int phi_check_law(int law) {
+    if (law == NBX_LAW_FMM_P2P) return fail(NBX_ERR_INVALID, "NBX_LAW_FMM_P2P has no potential: its smoothed magnitude with unsmoothed direction is no gradient");
+    if (law != NBX_LAW_BRUTE && law != NBX_LAW_TREE_LEAF && law != NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
+    return NBX_OK;
+}
+
+// The phi block for the structure as it stands.  Nothing on the device uses the block: every potential call ends synchronised.
+static int plan_fit_phi(nbx_leaf_plan* p) {
+    p->phi_valid = false;
+    const size_t nblk = (p->n + 255) / 256;
+    const size_t sizes[3] = {p->pslots * sizeof(double), p->n * sizeof(double), 2 * nblk * sizeof(double)};
+    const auto cut = carve(sizes);
+    NBX_HIP_TRY(nbx_block::fit(p->phi_block, leaf_pool(), p->device, cut.total));
+    char* const base = p->phi_block.get();
+    p->phi_slot = cut.at<double>(base, 0);
+    p->phi_body = cut.at<double>(base, 1);
+    p->phi_part = cut.at<double>(base, 2);
+    return NBX_OK;
+}
+
+// behind the gather on s: moments (if the plan has cells), near + far potential, phi by body
+static int plan_launch_phi(nbx_leaf_plan* p, int law, hipStream_t s) {
+    if (p->far.n_cells) {
+        NBX_HIP_TRY(nbx_far::enqueue_moments(p->far, p->dim, s));
+        p->cells_evaluated = true;                          // the cells' records now belong to the positions just gathered
+        p->quads_evaluated = p->far.order == NBX_FAR_QUADRUPOLE;
+    }
+    NBX_HIP_TRY(hipMemsetAsync(p->phi_slot, 0, p->pslots ? p->pslots * sizeof(double) : 8, s));
+    nbx_phi::PhiDevice d;
+    d.xp = p->xp; d.pslots = (uint32_t)p->pslots; d.ops = p->ops; d.blocks = p->blocks; d.subs = p->subs;
+    d.n_blocks = (uint32_t)p->n_blocks; d.n_subs = (uint32_t)p->n_subs; d.phi = p->phi_slot; d.eps2 = plan_eps2(p);
+    NBX_HIP_TRY(nbx_phi::enqueue_near_phi(d, p->dim, law, s));
+    nbx_far::FarDevice f = p->far;
+    f.eps2 = plan_eps2(p);
+    NBX_HIP_TRY(nbx_phi::enqueue_far_phi(f, p->phi_slot, p->dim, law, s));
+    NBX_HIP_TRY(nbx_phi::enqueue_phi_by_body(p->phi_slot, p->body_slot, p->n, law == NBX_LAW_NEWTON ? 1.0 : 0.5, p->phi_body, s));
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_potentials(nbx_leaf_plan* p, const void* bodies, size_t stride_bytes, int law, double* phi_out) {
+    if (!p) return fail(NBX_ERR_INVALID, "plan is null");
+    if (int lrc = phi_check_law(law)) return lrc;
+    if ((!bodies || !phi_out) && p->n) return fail(NBX_ERR_INVALID, "null argument");
+    const size_t min_stride = (size_t)(2 * p->dim + 1) * sizeof(double);
+    if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
+        return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
+    if (int src = plan_needs_structure(p)) return src;
+    if (law == NBX_LAW_NEWTON) {   // one host pass over the masses about to be copied, as in nbx_leaf_plan_forces
+        double mass_max = 0.0;
+        const char* const m0 = static_cast<const char*>(bodies) + 2 * (size_t)p->dim * sizeof(double);
+        for (size_t i = 0; i < p->n; ++i) {
+            double m;
+            std::memcpy(&m, m0 + i * stride_bytes, sizeof m);
+            m = std::fabs(m);
+            if (!(m <= mass_max)) mass_max = m;      // a NaN stays: refused below
+        }
+        if (int lrc = plan_check_law(p, law, mass_max)) return lrc;
+    }
+    hipStream_t s = p->stream;
+    PlanScope in(p, s);
+    if (in.rc) return in.rc;
+    if (int rc = plan_fit_phi(p)) return rc;
+    const size_t bytes = p->n * stride_bytes;
+    if (bytes && bytes + 256 > p->phi_raw.bytes()) NBX_HIP_TRY(nbx_block::allocate(p->phi_raw, p->device, bytes + 256));
+    if (bytes) NBX_HIP_TRY(hipMemcpyAsync(p->phi_raw.get(), bodies, bytes, hipMemcpyHostToDevice, s));
+    NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
+    if (p->pslots)
+        NBX_HIP_TRY(nbx_near::enqueue_gather_staged(p->phi_raw.as<double>(), stride_bytes / sizeof(double), p->dim, p->pslot_body, p->pslots, p->xp, p->max_mass, s));
+    if (int rc = plan_launch_phi(p, law, s)) return rc;
+    if (p->n) NBX_HIP_TRY(hipMemcpyAsync(phi_out, p->phi_body, p->n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (int rc = plan_mark_done(p, s)) return rc;
+    NBX_HIP_TRY(hipStreamSynchronize(s));
+    p->phi_valid = true;
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_energy(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double* kinetic, double* potential) {
+    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
+    if (int lrc = phi_check_law(law)) return lrc;
+    if (int crc = plan_check_ctx(p, c)) return crc;
+    if (int src = plan_needs_structure(p)) return src;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
+    const size_t nblk = (p->n + 255) / 256;
+    std::vector<double> host;
+    try { host.resize(2 * nblk); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
+    hipStream_t s = c->stream;
+    PlanScope in(p, s);
+    if (in.rc) return in.rc;
+    if (int rc = plan_fit_phi(p)) return rc;
+    NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
+    if (int rc = plan_gather_resident(p, c, s)) return rc;
+    if (int rc = plan_launch_phi(p, law, s)) return rc;
+    NBX_HIP_TRY(nbx_phi::enqueue_energy_partials(p->phi_body, p->n, p->dim, c->pad, c->v64, c->m64, p->phi_part, s));
+    if (nblk) NBX_HIP_TRY(hipMemcpyAsync(host.data(), p->phi_part, 2 * nblk * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (int rc = plan_mark_done(p, s)) return rc;
+    NBX_HIP_TRY(hipStreamSynchronize(s));
+    p->phi_valid = true;
+    long double mv2 = 0.0L, mphi = 0.0L;                    // workgroup order over the device's per-workgroup sums: a fixed tree
+    for (size_t l = 0; l < nblk; ++l) { mv2 += host[l]; mphi += host[nblk + l]; }
+    if (kinetic) *kinetic = 0.5 * (double)mv2;
+    if (potential) *potential = (law == NBX_LAW_BRUTE ? 0.5 : -0.5) * G * (double)mphi;   // U = s (G / 2) sum_i m_i phi_i
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_get_potentials(nbx_leaf_plan* p, double* phi_out) {
+    if (!p || (!phi_out && p->n)) return fail(NBX_ERR_INVALID, "null argument");
+    if (!p->phi_valid) return fail(NBX_ERR_STATE, "no potential call on this plan yet (nbx_leaf_plan_energy / nbx_leaf_plan_potentials)");
+    PlanScope in(p, p->stream);
+    if (in.rc) return in.rc;
+    if (p->n) NBX_HIP_TRY(hipMemcpyAsync(phi_out, p->phi_body, p->n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    NBX_HIP_TRY(hipStreamSynchronize(p->stream));
+    return plan_mark_done(p, p->stream);
 }
 
 }  // extern "C"

@@ -228,6 +228,18 @@ void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double t
     for (std::size_t l = 0; l < *n_leaves; ++l) *largest_leaf = std::max<std::size_t>(*largest_leaf, offsets[l + 1] - offsets[l]);
 }
 
+template <int D>
+void barnes_hut_hip_tree_energy(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int depth, int far_order, double* kinetic, double* potential) {
+    if (kinetic) *kinetic = 0.0;
+    if (potential) *potential = 0.0;
+    if (bodies.empty()) return;
+    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_tree_energy", leaf_capacity, far_order);
+    const int rc = nbx_leaf_plan_energy(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, kinetic, potential);
+    if (rc != NBX_OK) raise_leaf("barnes_hut_hip_tree_energy", rc);
+}
+template void barnes_hut_hip_tree_energy<2>(const std::vector<Body<2>>&, double, int, int, int, double*, double*);
+template void barnes_hut_hip_tree_energy<3>(const std::vector<Body<3>>&, double, int, int, int, double*, double*);
+
 // ---- softened Newtonian gravity through the tree ----
 template <int D>
 BarnesHutNewtonHip<D>::BarnesHutNewtonHip(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int depth, int far_order, double G, double epsilon)
@@ -270,6 +282,11 @@ template <int D>
 void BarnesHutNewtonHip<D>::energy(double* kinetic, double* potential) {
     const int rc = nbx_ctx_energy(ctx_, G_, kinetic, potential);
     if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::energy", rc);
+}
+template <int D>
+void BarnesHutNewtonHip<D>::tree_energy(double* kinetic, double* potential) {
+    const int rc = nbx_leaf_plan_energy(plan_, ctx_, NBX_LAW_NEWTON, G_, kinetic, potential);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::tree_energy", rc);
 }
 template <int D>
 void BarnesHutNewtonHip<D>::download(std::vector<Body<D>>& bodies) {

@@ -135,7 +135,9 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
 // The same system kept on the device between chunks of steps: a context with the bodies and a plan with the octree built from them
 // (leaf_capacity < 0: fixed depth, depth 0 = barnes_hut_hip_depth; otherwise the adaptive tree down to `depth`).  energy() is the
 // context's (nbx_ctx_energy) under the Newtonian law and the same epsilon -- the context's own law and softening are set for that
-// call alone; the forces and the steps are the plan's.
+// call alone; the forces and the steps are the plan's.  tree_energy() is the plan's (nbx_leaf_plan_energy): the potential through the
+// tree's own near lists and far cells at the object's far order and epsilon, O(N log N) like a step, on the tree as it stands (it does
+// not rebuild) -- an observer: the steps that follow give the bits they would have given without it.
 template <int D>
 class BarnesHutNewtonHip {
 public:
@@ -146,6 +148,7 @@ public:
     std::vector<Vector<D>> forces();                          // of the bodies as they stand, on the tree as it stands
     void step(double dt, int nsteps, int rebuild_every = 1);  // nbx_leaf_plan_step_octree
     void energy(double* kinetic, double* potential);          // synchronises
+    void tree_energy(double* kinetic, double* potential);     // synchronises
     void download(std::vector<Body<D>>& bodies);
 private:
     struct nbx_ctx* ctx_ = nullptr;
@@ -153,6 +156,13 @@ private:
     std::size_t n_ = 0;
     double G_ = 0.0;
 };
+
+// The energy of `bodies` through a Barnes-Hut tree built on the device under the REFERENCE law the tree rows above evaluate
+// (NBX_LAW_TREE_LEAF, the reference's G): K = sum m v^2 / 2 and U = -(G / 2) sum_i m_i phi_i with phi over the tree's near lists and far
+// cells (nbx_leaf_plan_energy).  leaf_capacity < 0: the fixed-depth tree (depth 0 = barnes_hut_hip_depth); otherwise the adaptive one down
+// to `depth`.  The reference-law trees have no object that lives between steps, so this is a call like theirs: bodies in, a new tree.
+template <int D>
+void barnes_hut_hip_tree_energy(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int depth, int far_order, double* kinetic, double* potential);
 
 // The yardstick of the Newtonian rows: the same law summed over ALL pairs by a context (nbx_ctx_set_law(NBX_FORCE_LAW_NEWTON),
 // nbx_ctx_set_softening, nbx_ctx_compute_accel, nbx_ctx_get_forces) -- no tree, no plan.

@@ -46,6 +46,7 @@ struct Options {
     bool have_e0 = false;
     double G = ::G;                 // --G: coupling constant of the HIP stepping loop (default: the reference's)
     int energy_every = 0;           // --energy-every k: log E and |dE/E0| every k steps of the loop
+    bool energy_tree = false;       // --energy-tree: behind each energy line of the tree's Newtonian step loop, the same line from the tree itself
     std::string integrator = "kd";  // --integrator kd|kdk: kick-drift as the reference helpers are ordered, or kick-drift-kick (extension)
     std::string law = "reference";  // --law reference|newton: pair law of the stepping loop (newton: extension, needs --softening)
     double softening = 0.0;         // --softening eps: Plummer-softened law in the stepping loop (extension; 0 = reference law)
@@ -421,12 +422,26 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                     std::vector<Body<D>> state = bodies;
                     const long long step_us = safely_execute(log, name + "_steps", [&] {
                         BarnesHutNewtonHip<D> sim(bodies, opt.theta, capacity, depth, order, opt.G, opt.softening);
-                        double ke = 0.0, pe = 0.0, e0 = 0.0;
+                        double ke = 0.0, pe = 0.0, e0 = 0.0, e0_tree = 0.0;
                         const int chunk = opt.energy_every > 0 ? opt.energy_every : opt.steps;
+                        // --energy-tree: the energy through the plan's own lists (nbx_leaf_plan_energy, O(N log N)) behind the all-pairs line,
+                        // and how far the two potentials are apart
+                        auto tree_line = [&](int step) {
+                            double kt = 0.0, pt = 0.0;
+                            sim.tree_energy(&kt, &pt);
+                            if (step == 0) e0_tree = kt + pt;
+                            out << "step " << step << "  E_tree = " << std::setprecision(12) << kt + pt;
+                            if (step == 0) out << "  (kinetic " << kt << ", potential " << pt << ")";
+                            else out << "  |dE/E0| = " << std::setprecision(3) << std::abs((kt + pt - e0_tree) / e0_tree) << std::setprecision(6) << "  (kinetic " << kt
+                                     << ", potential " << pt << ", 2K/|U| " << 2.0 * kt / std::abs(pt) << ")";
+                            out << "  |U_tree - U| / |U| = " << std::scientific << std::setprecision(3) << std::abs((pt - pe) / pe) << std::fixed << std::setprecision(6)
+                                << std::endl;
+                        };
                         if (opt.energy_every > 0) {
                             sim.energy(&ke, &pe);
                             e0 = ke + pe;
                             out << "step 0  E = " << std::setprecision(12) << e0 << "  (kinetic " << ke << ", potential " << pe << ")" << std::endl;
+                            if (opt.energy_tree) tree_line(0);
                         }
                         for (int done = 0; done < opt.steps;) {
                             const int k = std::min(chunk, opt.steps - done);
@@ -437,6 +452,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                                 out << "step " << done << "  E = " << std::setprecision(12) << ke + pe << "  |dE/E0| = " << std::setprecision(3)
                                     << std::abs((ke + pe - e0) / e0) << std::setprecision(6) << "  (kinetic " << ke << ", potential " << pe
                                     << ", 2K/|U| " << 2.0 * ke / std::abs(pe) << ")" << std::endl;
+                                if (opt.energy_tree) tree_line(done);
                             }
                         }
                         sim.download(state);
@@ -630,6 +646,7 @@ void usage(const char* argv0) {
               << "      --leaf-cap <k>  -m t builds the ADAPTIVE octree: leaves of at most k bodies, --depth the deepest level (default 10); 0: fixed depth" << std::endl
               << "      --far-order <0|1> 1: -m t runs its rows again with the far cells' second moments (quadrupole term; rows named ..._quad)" << std::endl
               << "      --energy-every <k> Log total energy and |dE/E0| every k steps (potential matching the selected law)" << std::endl
+              << "      --energy-tree      With -m t --law newton: behind each energy line, an E_tree line from the tree's own lists and the two potentials' relative difference" << std::endl
               << "      --refine <tol>  Per-body relative tolerance of the HIP rows: fp32 for all bodies + fp64 re-evaluation of those whose" << std::endl
               << "                      fp32 sum cannot be trusted to <tol> (default 1e-5: every body within 1e-5 of the sequential reference);" << std::endl
               << "                      0 = plain fp32" << std::endl
@@ -696,6 +713,8 @@ int main(int argc, char* argv[]) {
             opt.G = std::stod(argv[++i]);
         } else if (arg == "--energy-every" && has_value) {
             opt.energy_every = std::stoi(argv[++i]);
+        } else if (arg == "--energy-tree") {
+            opt.energy_tree = true;
         } else if (arg == "--softening" && has_value) {
             opt.softening = std::stod(argv[++i]);
         } else if (arg == "--integrator" && has_value) {

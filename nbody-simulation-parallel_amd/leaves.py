@@ -477,3 +477,115 @@ def near_sums(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, list_offs
                 out[ids, k] += np.einsum("ij,ij->i", w, d[k])
             S[ids] += np.einsum("ij,ij->i", np.abs(w), np.sqrt(r2))
     return out, S
+
+
+# ---- the potential through a plan: the fp64 specification of nbx_leaf_plan_energy / _potentials (include/nbody_hip.h) ----------
+# Plain numpy, nothing shared with the device code: these are what the tests hold csrc/leaf_phi_kernel.hip to.  The laws' sums
+# (near_sums, far_sums, the kernels) are the gradients of these with respect to the target's position.
+
+_POTENTIAL_LAWS = {"newton": None, "brute": 1e-10, "tree_leaf": 1e-9, "reference": 1e-9}   # r^2 below which the law skips a pair
+
+
+def _potential_law(law: str):
+    if law not in _POTENTIAL_LAWS:
+        raise ValueError("law must be 'newton', 'brute', 'tree_leaf' or 'reference' (= 'tree_leaf'); NBX_LAW_FMM_P2P has no potential")
+    return _POTENTIAL_LAWS[law]
+
+
+def near_potentials(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, list_offsets, list_sources, law: str, eps: float = 0.0):
+    """Every body's near potential per unit G m_i, fp64: for body i of target leaf t, the sum over the bodies j != i of the leaves on
+    t's list (a repeated leaf counts twice) of m_j w(r_ij):
+        law="newton":              w = 1 / sqrt(r^2 + eps^2); the body ITSELF is left out (by identity), a different body at the
+                                   same position counts m_j / eps;
+        law="brute" / "tree_leaf": w = 1 / (2 r^2); pairs with r^2 < 1e-10 / 1e-9 are left out (the body itself among them).
+    Returns (phi[n], S[n]) with S_i the sum of the terms' magnitudes, the scale of a backward-error bound on the fp32 pair terms.
+    Bodies in no leaf get zeros."""
+    skip = _potential_law(law)
+    lo, lb = np.asarray(leaf_offsets, dtype=np.int64), np.asarray(leaf_bodies, dtype=np.int64)
+    so, ss = np.asarray(list_offsets, dtype=np.int64), np.asarray(list_sources, dtype=np.int64)
+    x, m = np.asarray(bodies[:, :dim], dtype=np.float64), np.asarray(bodies[:, -1], dtype=np.float64)
+    e2 = float(eps) ** 2
+    phi, S = np.zeros(bodies.shape[0]), np.zeros(bodies.shape[0])
+    for t in range(lo.size - 1):
+        ids = lb[lo[t]:lo[t + 1]]
+        if not ids.size or so[t + 1] == so[t]:
+            continue
+        src = np.concatenate([lb[lo[l]:lo[l + 1]] for l in ss[so[t]:so[t + 1]]])
+        for j0 in range(0, src.size, 8192):                       # bounded temporaries: [targets, 8192]
+            sj = src[j0:j0 + 8192]
+            r2 = np.zeros((ids.size, sj.size))
+            for k in range(dim):
+                d = x[sj, k][None, :] - x[ids, k][:, None]
+                r2 += d * d
+            if skip is None:
+                w = np.where(sj[None, :] == ids[:, None], 0.0, m[None, sj] / np.sqrt(np.where(sj[None, :] == ids[:, None], 1.0, r2 + e2)))
+            else:
+                keep = r2 >= skip
+                w = np.where(keep, 0.5 * m[None, sj] / np.where(keep, r2, 1.0), 0.0)
+            phi[ids] += w.sum(axis=1)
+            S[ids] += np.abs(w).sum(axis=1)
+    return phi, S
+
+
+def _far_quadratic_form(R: np.ndarray, q: np.ndarray):
+    """(tr q, R^T q R) for q in the stored order."""
+    dim = R.shape[-1]
+    tr = q[..., 0] + q[..., 1] + (q[..., 2] if dim == 3 else 0)
+    RqR = 0
+    for k, (a, b) in enumerate(_quad_pairs(dim)):
+        RqR = RqR + (1 if a == b else 2) * q[..., k] * R[..., a] * R[..., b]
+    return tr, RqR
+
+
+def far_potential_correction(R: np.ndarray, M, Q: np.ndarray, law: str = "reference", eps: float = 0.0) -> np.ndarray:
+    """What a cell of mass M and central second moments Q (stored order) adds to its monopole potential for a target at -R from its
+    centre of mass (R = com - p_i), per unit G m_i, with q = Q / M and t = tr q:
+        reference laws:  (M / (2 r^2)) [ -t / r^2 + 4 R^T q R / r^4 ]                 on top of M / (2 r^2)
+        law="newton":    (M / rho) [ -t / (2 rho^2) + (3/2) R^T q R / rho^4 ]         on top of M / rho, rho^2 = r^2 + eps^2.
+    Its gradient with respect to p_i is far_correction.  R[..., dim], M[...], Q[..., dim (dim + 1) / 2] broadcast together; zeros
+    where M == 0.  No skip is applied here (far_potentials does)."""
+    newton = _potential_law(law) is None
+    R = np.asarray(R, dtype=np.float64)
+    M = np.asarray(M, dtype=np.float64)
+    Q = np.asarray(Q, dtype=np.float64)
+    live = M != 0
+    q = Q / np.where(live, M, 1)[..., None]
+    tr, RqR = _far_quadratic_form(R, q)
+    r2 = (R * R).sum(axis=-1)
+    if newton:
+        rho2 = r2 + float(eps) ** 2
+        out = (M / np.sqrt(rho2)) * (-0.5 * tr / rho2 + 1.5 * RqR / rho2 ** 2)
+    else:
+        out = (0.5 * M / r2) * (-tr / r2 + 4.0 * RqR / r2 ** 2)
+    return np.where(live, out, 0.0)
+
+
+def far_potentials(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, cell_first_leaf, cell_leaf_count, far_offsets, far_cells,
+                   order: int = 0, law: str = "reference", eps: float = 0.0, moments=None):
+    """Every body's far potential per unit G m_i, fp64: the sum over the cells c of its leaf's far list of M_c / (2 r^2) (reference
+    laws) or M_c / sqrt(r^2 + eps^2) (law="newton"), plus far_potential_correction at order 1.  Where a reference law skips the pair
+    with the pseudo-body (r^2 below its threshold) the whole term is 0; a massless cell adds 0.  Returns (phi[n], S[n]), S_i the sum
+    of the terms' magnitudes.  moments: cell_moments' result, if at hand."""
+    skip = _potential_law(law)
+    lo, lb = np.asarray(leaf_offsets, dtype=np.int64), np.asarray(leaf_bodies, dtype=np.int64)
+    fo, fc = np.asarray(far_offsets, dtype=np.int64), np.asarray(far_cells, dtype=np.int64)
+    M, com, Q = moments if moments is not None else cell_moments(bodies, dim, lo, lb, cell_first_leaf, cell_leaf_count)
+    phi, S = np.zeros(bodies.shape[0]), np.zeros(bodies.shape[0])
+    for t in range(lo.size - 1):
+        ids, c = lb[lo[t]:lo[t + 1]], fc[fo[t]:fo[t + 1]]
+        c = c[M[c] != 0]
+        if not ids.size or not c.size:
+            continue
+        R = com[None, c, :] - np.asarray(bodies[ids, None, :dim], dtype=np.float64)
+        r2 = (R * R).sum(axis=2)
+        if skip is None:
+            term = M[None, c] / np.sqrt(r2 + float(eps) ** 2)
+        else:
+            term = 0.5 * M[None, c] / np.where(r2 >= skip, r2, 1.0)
+        if order == 1:
+            term = term + far_potential_correction(np.where((r2 > 0)[..., None], R, 1.0), M[None, c], Q[None, c, :], law, eps)
+        if skip is not None:
+            term = np.where(r2 >= skip, term, 0.0)
+        phi[ids] = term.sum(axis=1)
+        S[ids] = np.abs(term).sum(axis=1)
+    return phi, S

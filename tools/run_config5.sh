@@ -12,6 +12,8 @@
 #   METHOD=tree LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # the same sphere through the adaptive Barnes-Hut tree on
 #                                              # one GPU (-m t --leaf-cap 32 --far-order 1): its BarnesHut_HIP_adaptive_newton[_quad] rows,
 #                                              # step loops and energy lines; segments (LOAD, E0) are the all-pairs loop's alone
+#   METHOD=tree ENERGY=tree LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # ... with an E_tree line behind every energy line:
+#                                              # the energy through the tree's own lists (--energy-tree) and the two potentials' difference
 # A run can be cut into segments where a job may not last 1000 steps (one GPU: 3.5 s per step):
 #   STEPS=250 DUMP=seg1 tools/run_config5.sh
 #   STEPS=250 LOAD=seg1_Leapfrog_HIP.f64 STEP_OFFSET=250 E0=<E of step 0> DUMP=seg2 tools/run_config5.sh   ... and so on;
@@ -29,6 +31,7 @@ SOFTENING="${SOFTENING:-0}"
 LAW="${LAW:-reference}"
 METHOD="${METHOD:-brute}"            # brute = the all-pairs loop (-m g); tree = the adaptive octree on one GPU (-m t --leaf-cap 32 --far-order 1)
 INTEGRATOR="${INTEGRATOR:-kd}"       # kd = the reference helpers' order (kick, drift); kdk = synchronised leapfrog (extension)
+ENERGY="${ENERGY:-allpairs}"         # with METHOD=tree: tree = also log the energy through the tree itself (--energy-tree)
 LOAD="${LOAD:-}"; STEP_OFFSET="${STEP_OFFSET:-0}"; E0="${E0:-}"; DUMP="${DUMP:-}"
 OUT="${OUT:-gpurun_out/config5_${GPUS}gpu_${STEPS}steps.log}"
 mkdir -p "$(dirname "$OUT")"
@@ -37,8 +40,13 @@ if [ -n "$DEVICES" ]; then where=(--devices "$DEVICES"); else where=(--gpus "$GP
 [ -n "$LOAD" ] && where+=(--load "$LOAD" --step-offset "$STEP_OFFSET")
 [ -n "$E0" ] && where+=(--e0 "$E0")
 [ -n "$DUMP" ] && where+=(--dump "$DUMP")
+if [ "$ENERGY" != allpairs ] && [ "$ENERGY" != tree ]; then
+    echo "ENERGY must be allpairs or tree" >&2; exit 1
+fi
 if [ "$METHOD" = tree ]; then
-    ./nbody_sim -N "$N" -d 3 -m t --leaf-cap 32 --far-order 1 --init plummer --seed 5 --G "$G" --law "$LAW" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" | tee "$OUT"
+    energy=()
+    [ "$ENERGY" = tree ] && energy+=(--energy-tree)
+    ./nbody_sim -N "$N" -d 3 -m t --leaf-cap 32 --far-order 1 --init plummer --seed 5 --G "$G" --law "$LAW" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" ${energy[@]+"${energy[@]}"} | tee "$OUT"
     grep -E "^step |Time taken|relative force error|ms per step" "$OUT" > "${OUT%.log}.summary.txt"
     echo "summary: ${OUT%.log}.summary.txt"
     exit 0
