@@ -326,6 +326,47 @@ int nbx_leaf_plan_get_structure(nbx_leaf_plan* plan, uint32_t* leaf_offsets, uin
  * sums and the last structure built. */
 int nbx_leaf_plan_step_octree(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, double dt, int nsteps, int rebuild_every);
 
+/* ---- kick-drift-kick through a plan -------------------------------------------------------------------------------------------
+ * nbx_leaf_plan_kick_drift / _step / _step_octree run the reference helpers' order, kick then drift: first order in dt, and x and v
+ * are never at one time level.  The calls below are the synchronised second-order leapfrog through the same sums -- the plan's twin
+ * of nbx_ctx_kick_drift2 / nbx_ctx_step_kdk.  They add to the ABI; every call above keeps its bits.
+ *
+ * nbx_leaf_plan_kick_drift2: nbx_leaf_plan_kick_drift with the kick's and the drift's step apart, from the LAST evaluation's sums:
+ *       v += (F / m) dt_kick;  x += v dt_drift;  the fp32 source copy follows x
+ * F = +-(G m_i) x the sum as nbx_leaf_plan_kick_drift forms it; dt_kick == dt_drift gives that call's bits; a body in no leaf has
+ * F = 0 and drifts with its velocity.  dt_drift == 0 is a PURE KICK: no position is read or written (a velocity that is not finite
+ * cannot reach one through inf * 0), the context's bodies have not moved, and the plan's structure, the context's accelerations
+ * and its close-set lists stay valid.  Asynchronous on the context's stream.  Refusals are nbx_leaf_plan_kick_drift's:
+ * NBX_ERR_INVALID for a null argument or a context of the wrong device, dimension, body count or shard count; NBX_ERR_STATE before
+ * the first evaluation and when the last evaluation was not made from `ctx`.
+ *
+ * nbx_leaf_plan_step_kdk: nsteps steps of
+ *       F K(dt/2) D(dt) [ F K(dt) D(dt) ]^(nsteps-1) F K(dt/2)
+ * with the structure standing (F = nbx_leaf_plan_forces_ctx(NULL, NULL), K D = nbx_leaf_plan_kick_drift2): adjacent half-kicks are
+ * merged into one multiply by dt, as in nbx_ctx_step_kdk, so nsteps steps cost nsteps + 1 evaluations.  The opening evaluation is
+ * always made -- a plan does not try to know whether its sums are current; a caller who chains calls and wants to save it spells the
+ * sequence out with _forces_ctx and _kick_drift2.  TIME LEVELS: afterwards x and v are BOTH at t0 + nsteps dt, and the plan holds the
+ * sums of those final positions, so nbx_leaf_plan_get_forces, _max_accel and (with nbx_leaf_plan_energy) the energies all refer to
+ * the state the context holds.  Asynchronous.  nsteps == 0 does nothing.  Refusals, before anything is launched, are
+ * nbx_leaf_plan_step's (NBX_LAW_NEWTON: nbx_leaf_plan_set_softening's rules).
+ *
+ * nbx_leaf_plan_step_octree_kdk: the same sequence with rebuilds.  Evaluation number e = 0 .. nsteps is preceded by
+ * nbx_leaf_plan_rebuild_octree when rebuild_every > 0 and e % rebuild_every == 0; the closing half-kick follows an evaluation on
+ * the structure standing then, so the inverse map and the sums always belong together.  rebuild_every = 0 never rebuilds and
+ * equals nbx_leaf_plan_step_kdk.  Far order and softening survive, as through nbx_leaf_plan_step_octree, whose refusals these are
+ * (NBX_ERR_STATE for rebuild_every > 0 on a plan not made by nbx_leaf_plan_create_octree). */
+int nbx_leaf_plan_kick_drift2(nbx_leaf_plan* plan, nbx_ctx* ctx, double dt_kick, double dt_drift);
+int nbx_leaf_plan_step_kdk(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, double dt, int nsteps);
+int nbx_leaf_plan_step_octree_kdk(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, double dt, int nsteps, int rebuild_every);
+/* The largest acceleration magnitude of the LAST force evaluation -- what a step size is chosen from -- reduced on the device:
+ *       *a_max = max over the bodies that have a slot of  |G| sqrt(sum_k sum_i[k]^2)
+ * per unit mass (|F_i| / m_i), fp64, under the G given to that evaluation; bodies in no leaf count as 0; a sum that is not finite
+ * makes the result not finite (a NaN orders above infinity) instead of vanishing.  An OBSERVER like the potential calls: it
+ * synchronises and changes neither the sums, the record of the last evaluation nor the context.  8 bytes cross PCIe.  A plan never
+ * asked allocates nothing for it.  NBX_ERR_INVALID for a null argument; NBX_ERR_STATE before the first evaluation (or after a
+ * rebuild without one) and when the context of the last evaluation no longer exists. */
+int nbx_leaf_plan_max_accel(nbx_leaf_plan* plan, double* a_max);
+
 /* ---- the potential through a plan -------------------------------------------------------------------------------------------
  * What the plan's sums are the gradient of, through the same near lists and far cells, in O(list length) like the forces.  Per unit
  * G m_i, body i of target leaf t has

@@ -64,6 +64,10 @@ ABI = [
     ("nbx_leaf_plan_structure_sizes", _i, [_vp, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz)]),
     ("nbx_leaf_plan_get_structure", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("nbx_leaf_plan_step_octree", _i, [_vp, _vp, _i, _d, _d, _i, _i]),
+    ("nbx_leaf_plan_kick_drift2", _i, [_vp, _vp, _d, _d]),
+    ("nbx_leaf_plan_step_kdk", _i, [_vp, _vp, _i, _d, _d, _i]),
+    ("nbx_leaf_plan_step_octree_kdk", _i, [_vp, _vp, _i, _d, _d, _i, _i]),
+    ("nbx_leaf_plan_max_accel", _i, [_vp, _pd]),
     ("nbx_leaf_plan_potentials", _i, [_vp, _vp, _sz, _i, _vp]),
     ("nbx_leaf_plan_energy", _i, [_vp, _vp, _i, _d, _pd, _pd]),
     ("nbx_leaf_plan_get_potentials", _i, [_vp, _vp]),
@@ -416,6 +420,29 @@ class LeafPlan:
     def step(self, ctx: "Context", law: int, G: float, dt: float, nsteps: int):
         """nsteps x {forces_ctx(fetch=False); kick_drift} in one call (nbx_leaf_plan_step)."""
         self._ck(self.lib.nbx_leaf_plan_step(self.h, ctx.h, int(law), float(G), float(dt), int(nsteps)), "nbx_leaf_plan_step")
+
+    def kick_drift2(self, ctx: "Context", dt_kick: float, dt_drift: float):
+        """v += (F / m) dt_kick; x += v dt_drift from the last evaluation's sums (nbx_leaf_plan_kick_drift2).  dt_drift = 0 is a
+        pure kick: no position is touched and the context's bodies count as not moved."""
+        self._ck(self.lib.nbx_leaf_plan_kick_drift2(self.h, ctx.h, float(dt_kick), float(dt_drift)), "nbx_leaf_plan_kick_drift2")
+
+    def step_kdk(self, ctx: "Context", law: int, G: float, dt: float, nsteps: int):
+        """nsteps kick-drift-kick steps with the structure standing, nsteps + 1 evaluations (nbx_leaf_plan_step_kdk): afterwards
+        positions and velocities are at the same time, and the plan holds the sums of the final positions."""
+        self._ck(self.lib.nbx_leaf_plan_step_kdk(self.h, ctx.h, int(law), float(G), float(dt), int(nsteps)), "nbx_leaf_plan_step_kdk")
+
+    def step_octree_kdk(self, ctx: "Context", law: int, G: float, dt: float, nsteps: int, rebuild_every: int = 1):
+        """step_kdk with the octree built again before every `rebuild_every`-th evaluation, counted from 0
+        (nbx_leaf_plan_step_octree_kdk); rebuild_every = 0 is step_kdk."""
+        self._ck(self.lib.nbx_leaf_plan_step_octree_kdk(self.h, ctx.h, int(law), float(G), float(dt), int(nsteps), int(rebuild_every)),
+                 "nbx_leaf_plan_step_octree_kdk")
+
+    def max_accel(self) -> float:
+        """max_i |F_i| / m_i of the last force evaluation over the bodies in a leaf, reduced on the device (nbx_leaf_plan_max_accel).
+        An observer: the sums and the context stay as they are."""
+        v = ctypes.c_double(0.0)
+        self._ck(self.lib.nbx_leaf_plan_max_accel(self.h, ctypes.byref(v)), "nbx_leaf_plan_max_accel")
+        return v.value
 
     def set_cells(self, cell_first_leaf, cell_leaf_count, far_offsets, far_cells):
         """The plan's far field (nbx_leaf_plan_set_cells): cells as leaf ranges and a CSR far list per target leaf; every evaluation

@@ -125,6 +125,8 @@ struct nbx_leaf_plan {
     double* phi_part = nullptr;     // [2][ceil(n / 256)]
     bool phi_valid = false;         // a potential call has gone through
     Block phi_raw;                  // staged Body<D> array of nbx_leaf_plan_potentials -- not `raw`: the masses of the last force evaluation may live there
+    // ---- the largest acceleration (nbx_leaf_plan_max_accel): the reduction's 8-byte word, allocated when a caller first asks ----
+    Block amax_block;
 };
 
 namespace {
@@ -373,6 +375,13 @@ SlotKickArgs slot_kick_args(const nbx_leaf_plan* p, const nbx_ctx* c, double sig
     SlotKickArgs k;
     k.sums = p->sums; k.body_slot = p->body_slot; k.pslots = (uint32_t)p->pslots; k.dim = p->dim; k.pad = c->pad; k.count = c->count;
     k.signedG = signedG; k.dt = dt; k.x64 = c->x64; k.v64 = c->v64; k.m64 = c->m64; k.pos_chunk = c->pos_all;
+    return k;
+}
+
+SlotKick2Args slot_kick2_args(const nbx_leaf_plan* p, const nbx_ctx* c, double signedG, double dt_kick, double dt_drift) {
+    SlotKick2Args k;
+    k.sums = p->sums; k.body_slot = p->body_slot; k.pslots = (uint32_t)p->pslots; k.dim = p->dim; k.pad = c->pad; k.count = c->count;
+    k.signedG = signedG; k.dt_kick = dt_kick; k.dt_drift = dt_drift; k.x64 = c->x64; k.v64 = c->v64; k.m64 = c->m64; k.pos_chunk = c->pos_all;
     return k;
 }
 
@@ -801,6 +810,7 @@ int nbx_leaf_plan_destroy(nbx_leaf_plan* p) {
     p->raw.release(all_idle);
     p->phi_block.release(all_idle);
     p->phi_raw.release(all_idle);
+    p->amax_block.release(all_idle);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     if (p->done) (void)hipEventDestroy(p->done);
@@ -967,6 +977,92 @@ int nbx_leaf_plan_step_octree(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, d
         if ((rc = plan_mark_done(p, s))) return rc;
     }
     return NBX_OK;
+}
+
+// ---- kick-drift-kick (include/nbody_hip.h "kick-drift-kick through a plan") ---------------------------------------------------
+int nbx_leaf_plan_kick_drift2(nbx_leaf_plan* p, nbx_ctx* c, double dt_kick, double dt_drift) {
+    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
+    if (!p->evaluated) return fail(NBX_ERR_STATE, "evaluate the leaf sums before kick_drift2");
+    if (int crc = plan_check_ctx(p, c, false)) return crc;
+    if (p->last_ctx_id != c->id) return fail(NBX_ERR_STATE, "the last evaluation was not made from this context");
+    hipStream_t s = c->stream;
+    PlanScope in(p, s);
+    if (in.rc) return in.rc;
+    NBX_HIP_TRY(launch_kick_drift_slots2(slot_kick2_args(p, c, p->last_signedG, dt_kick, dt_drift), s));
+    if (dt_drift != 0.0) ctx_bodies_moved(c);   // a pure kick leaves the positions -- and with them the context's accelerations and lists -- valid
+    return plan_mark_done(p, s);
+}
+
+// evaluation number e of 0 .. nsteps and the kick (and drift) behind it: F K(dt/2) D(dt) [F K(dt) D(dt)]^(n-1) F K(dt/2), the
+// adjacent half-kicks merged into one multiply by dt (nbx_ctx_step_kdk's form)
+static int plan_enqueue_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double signedG, double dt, int e, int nsteps, hipStream_t s) {
+    NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
+    if (int rc = plan_gather_resident(p, c, s)) return rc;
+    if (int rc = plan_launch_pairs(p, law, s, false)) return rc;
+    const double dt_kick = e == 0 || e == nsteps ? 0.5 * dt : dt;
+    NBX_HIP_TRY(launch_kick_drift_slots2(slot_kick2_args(p, c, signedG, dt_kick, e < nsteps ? dt : 0.0), s));
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_step_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps) {
+    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
+    if (nsteps < 0) return fail(NBX_ERR_INVALID, "nsteps must be >= 0");
+    if (int crc = plan_check_ctx(p, c)) return crc;
+    if (nsteps == 0) return NBX_OK;
+    if (int src = plan_needs_structure(p)) return src;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
+    hipStream_t s = c->stream;
+    PlanScope in(p, s);
+    if (in.rc) return in.rc;
+    const double signedG = signed_G(law, G);
+    for (int e = 0; e <= nsteps; ++e)
+        if (int rc = plan_enqueue_kdk(p, c, law, signedG, dt, e, nsteps, s)) return rc;
+    plan_record_evaluation(p, law, signedG, c);
+    ctx_bodies_moved(c);
+    return plan_mark_done(p, s);
+}
+
+int nbx_leaf_plan_step_octree_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
+    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
+    if (nsteps < 0 || rebuild_every < 0) return fail(NBX_ERR_INVALID, "nsteps and rebuild_every must be >= 0");
+    if (int rc = plan_check_ctx(p, c)) return rc;
+    if (rebuild_every > 0 && !p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
+    if (nsteps == 0) return NBX_OK;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
+    hipStream_t s = c->stream;
+    PlanScope in(p, s);
+    if (in.rc) return in.rc;
+    const double signedG = signed_G(law, G);
+    for (int e = 0; e <= nsteps; ++e) {
+        int rc = rebuild_every > 0 && e % rebuild_every == 0 ? plan_build_octree(p, c) : NBX_OK;
+        if (!rc) rc = plan_needs_structure(p);
+        if (!rc) rc = plan_enqueue_kdk(p, c, law, signedG, dt, e, nsteps, s);
+        if (rc) return rc;
+        plan_record_evaluation(p, law, signedG, c);
+        if (e < nsteps) ctx_bodies_moved(c);
+        if ((rc = plan_mark_done(p, s))) return rc;
+    }
+    return NBX_OK;
+}
+
+// An observer like the potential calls: it reads the slot sums and the inverse map and writes its own 8-byte word.
+int nbx_leaf_plan_max_accel(nbx_leaf_plan* p, double* a_max) {
+    if (!p || !a_max) return fail(NBX_ERR_INVALID, "null argument");
+    if (!p->evaluated) return fail(NBX_ERR_STATE, "no evaluation on the device");
+    if (p->last_ctx_id && !nbx::ctx_alive(p->last_ctx_id))
+        return fail(NBX_ERR_STATE, "the context of the last evaluation no longer exists: evaluate again before asking for the largest acceleration");
+    PlanScope in(p, p->stream);   // the plan's own stream, behind the last evaluation's event (nbx_leaf_plan_get_forces)
+    if (in.rc) return in.rc;
+    if (!p->amax_block) NBX_HIP_TRY(nbx_block::allocate(p->amax_block, p->device, 256));
+    unsigned long long bits = 0ull;
+    NBX_HIP_TRY(launch_slot_accel_max(p->sums, p->body_slot, (uint32_t)p->pslots, p->dim, p->n, std::fabs(p->last_signedG),
+                                      p->amax_block.as<unsigned long long>(), p->stream));
+    NBX_HIP_TRY(hipMemcpyAsync(&bits, p->amax_block.get(), sizeof bits, hipMemcpyDeviceToHost, p->stream));
+    NBX_HIP_TRY(hipStreamSynchronize(p->stream));
+    std::memcpy(a_max, &bits, sizeof bits);
+    return plan_mark_done(p, p->stream);
 }
 
 int nbx_leaf_plan_set_cells(nbx_leaf_plan* p, const uint32_t* cell_first_leaf, const uint32_t* cell_leaf_count, size_t n_cells,

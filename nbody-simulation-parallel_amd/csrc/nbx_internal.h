@@ -266,6 +266,22 @@ struct SlotKickArgs {
     float* pos_chunk;
 };
 hipError_t launch_kick_drift_slots(const SlotKickArgs& k, hipStream_t stream);
+// the same with the kick's and the drift's step apart; dt_drift == 0 launches the pure kick, which touches no position
+struct SlotKick2Args {
+    const double* sums;        // [dim][pslots]
+    const uint32_t* body_slot; // [count]
+    uint32_t pslots;
+    int dim;
+    unsigned pad;
+    size_t count;
+    double signedG, dt_kick, dt_drift;
+    double* x64; double* v64; const double* m64;
+    float* pos_chunk;
+};
+hipError_t launch_kick_drift_slots2(const SlotKick2Args& k, hipStream_t stream);
+// *out (device, 8 bytes; zeroed here first) = bit pattern of max over the n bodies with a slot of absG * |sums[.][slot]|, fp64
+hipError_t launch_slot_accel_max(const double* sums, const uint32_t* body_slot, uint32_t pslots, int dim, size_t n, double absG,
+                                 unsigned long long* out, hipStream_t stream);
 
 // forces_out: AoS double[count][dim] on the device
 hipError_t launch_export_forces(const float* acc, int splits, int dim, unsigned pad, size_t count,

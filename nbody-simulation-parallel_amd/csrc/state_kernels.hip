@@ -113,6 +113,59 @@ __global__ __launch_bounds__(256) void kick_drift_slots_kernel(SlotKickArgs a) {
     a.pos_chunk[(size_t)k * a.pad + l] = (float)x;
 }
 
+// The same kernel with the kick's and the drift's step apart -- the building block of kick-drift-kick through a plan.  The expressions
+// and their order are kick_drift_slots_kernel's, so dt_kick == dt_drift gives its bits (this file is built without contraction: each
+// multiply and each add rounds by itself, there and here).  DRIFT = false is a pure kick: x64 and the fp32 position chunk are neither read nor written, so a velocity that is not
+// finite cannot reach a position through inf * 0.
+template <bool DRIFT>
+__global__ __launch_bounds__(256) void kick_drift_slots2_kernel(SlotKick2Args a) {
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= a.count) return;
+    const int k = (int)blockIdx.y;
+    const double m = a.m64[l];
+    const uint32_t slot = a.body_slot[l];
+    const double sum = slot == 0xffffffffu ? 0.0 : a.sums[(size_t)k * a.pslots + slot];
+    const double F = (a.signedG * m) * sum;
+    double v = a.v64[(size_t)k * a.pad + l];
+    v += (F / m) * a.dt_kick;
+    a.v64[(size_t)k * a.pad + l] = v;
+    if (DRIFT) {
+        double x = a.x64[(size_t)k * a.pad + l];
+        x += v * a.dt_drift;
+        a.x64[(size_t)k * a.pad + l] = x;
+        a.pos_chunk[(size_t)k * a.pad + l] = (float)x;
+    }
+}
+
+// The largest acceleration magnitude of the last evaluation, |signedG| * |sums[.][slot_i]|, over the bodies that have a slot (fp64).
+// pack_kernel's idiom: non-negative doubles order like their bit patterns and a NaN's pattern lies above infinity's, so a sum that
+// is not finite makes the result not finite; butterfly maxima over the wave, one LDS atomic per wave, one L2 atomic per workgroup.
+// Every lane stays for the shuffles (no early exit); lanes past n and bodies in no leaf carry 0.
+__global__ __launch_bounds__(256) void slot_accel_max_kernel(const double* __restrict__ sums, const uint32_t* __restrict__ body_slot,
+                                                             uint32_t pslots, int dim, size_t n, double absG,
+                                                             unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_max;
+    if (threadIdx.x == 0) s_max = 0ull;
+    __syncthreads();
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long ab = 0ull;
+    if (l < n) {
+        const uint32_t slot = body_slot[l];
+        if (slot != 0xffffffffu) {
+            double s2 = 0.0;
+            for (int k = 0; k < dim; ++k) { const double s = sums[(size_t)k * pslots + slot]; s2 += s * s; }
+            ab = (unsigned long long)__double_as_longlong(fabs(absG * sqrt(s2)));   // fabs: a NaN's sign bit goes too
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(ab, off);
+        ab = o > ab ? o : ab;
+    }
+    if ((threadIdx.x & 63u) == 0u && ab) atomicMax(&s_max, ab);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_max > *(volatile unsigned long long*)out) atomicMax(out, s_max);
+}
+
 __global__ __launch_bounds__(256) void export_forces_kernel(const float* __restrict__ acc, int splits, int dim,
                                                             unsigned pad, size_t count, double G,
                                                             const double* __restrict__ m64,
@@ -227,6 +280,22 @@ hipError_t launch_kick_drift(const KickDriftArgs& k, hipStream_t stream) {
 hipError_t launch_kick_drift_slots(const SlotKickArgs& k, hipStream_t stream) {
     if (k.count == 0) return hipSuccess;
     hipLaunchKernelGGL(kick_drift_slots_kernel, dim3(blocks_for(k.count), (unsigned)k.dim, 1), dim3(256), 0, stream, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_kick_drift_slots2(const SlotKick2Args& k, hipStream_t stream) {
+    if (k.count == 0) return hipSuccess;
+    const dim3 grid(blocks_for(k.count), (unsigned)k.dim, 1);
+    if (k.dt_drift != 0.0) hipLaunchKernelGGL(kick_drift_slots2_kernel<true>, grid, dim3(256), 0, stream, k);
+    else hipLaunchKernelGGL(kick_drift_slots2_kernel<false>, grid, dim3(256), 0, stream, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_slot_accel_max(const double* sums, const uint32_t* body_slot, uint32_t pslots, int dim, size_t n, double absG,
+                                 unsigned long long* out, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess || n == 0) return e;
+    hipLaunchKernelGGL(slot_accel_max_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, sums, body_slot, pslots, dim, n, absG, out);
     return hipGetLastError();
 }
 

@@ -99,6 +99,11 @@ void LeafPairSimulationHip<D>::step(LeafLaw law, double G, double dt, int nsteps
     if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::step", rc);
 }
 template <int D>
+void LeafPairSimulationHip<D>::step_kdk(LeafLaw law, double G, double dt, int nsteps) {
+    const int rc = nbx_leaf_plan_step_kdk(plan_, ctx_, static_cast<int>(law), G, dt, nsteps);
+    if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::step_kdk", rc);
+}
+template <int D>
 void LeafPairSimulationHip<D>::synchronize() {
     const int rc = nbx_ctx_synchronize(ctx_);
     if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::synchronize", rc);
@@ -189,6 +194,25 @@ void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth,
 }
 
 namespace {
+// the reference law's step loop under either integrator, the bodies brought back at the end
+template <int D>
+void tree_leaf_steps(OctreeOnDevice<D>& tree, std::vector<Body<D>>& bodies, double dt, int nsteps, int rebuild_every, TreeIntegrator integrator, const char* where) {
+    const int law = static_cast<int>(LeafLaw::TreeLeaf);
+    int rc = integrator == TreeIntegrator::KickDriftKick ? nbx_leaf_plan_step_octree_kdk(tree.plan, tree.ctx, law, NBX_REFERENCE_G, dt, nsteps, rebuild_every)
+                                                         : nbx_leaf_plan_step_octree(tree.plan, tree.ctx, law, NBX_REFERENCE_G, dt, nsteps, rebuild_every);
+    if (!rc) rc = nbx_ctx_download_bodies(tree.ctx, bodies.data(), sizeof(Body<D>));
+    if (rc != NBX_OK) raise_leaf(where, rc);
+}
+}  // namespace
+
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, TreeIntegrator integrator) {
+    if (bodies.empty()) return;
+    OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_steps", -1, far_order);
+    tree_leaf_steps<D>(tree, bodies, dt, nsteps, rebuild_every, integrator, "barnes_hut_hip_steps");
+}
+
+namespace {
 void check_capacity(int leaf_capacity, const char* where) {
     if (leaf_capacity < 0) throw std::runtime_error(std::string(where) + ": leaf_capacity must be >= 0");
 }
@@ -213,6 +237,15 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
     int rc = nbx_leaf_plan_step_octree(tree.plan, tree.ctx, static_cast<int>(LeafLaw::TreeLeaf), NBX_REFERENCE_G, dt, nsteps, rebuild_every);
     if (!rc) rc = nbx_ctx_download_bodies(tree.ctx, bodies.data(), sizeof(Body<D>));
     if (rc != NBX_OK) raise_leaf("barnes_hut_hip_adaptive_steps", rc);
+}
+
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every, int far_order,
+                                   TreeIntegrator integrator) {
+    check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_steps");
+    if (bodies.empty()) return;
+    OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_steps", leaf_capacity, far_order);
+    tree_leaf_steps<D>(tree, bodies, dt, nsteps, rebuild_every, integrator, "barnes_hut_hip_adaptive_steps");
 }
 
 template <int D>
@@ -279,6 +312,18 @@ void BarnesHutNewtonHip<D>::step(double dt, int nsteps, int rebuild_every) {
     if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::step", rc);
 }
 template <int D>
+void BarnesHutNewtonHip<D>::step_kdk(double dt, int nsteps, int rebuild_every) {
+    const int rc = nbx_leaf_plan_step_octree_kdk(plan_, ctx_, NBX_LAW_NEWTON, G_, dt, nsteps, rebuild_every);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::step_kdk", rc);
+}
+template <int D>
+double BarnesHutNewtonHip<D>::max_accel() {
+    double a = 0.0;
+    const int rc = nbx_leaf_plan_max_accel(plan_, &a);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::max_accel", rc);
+    return a;
+}
+template <int D>
 void BarnesHutNewtonHip<D>::energy(double* kinetic, double* potential) {
     const int rc = nbx_ctx_energy(ctx_, G_, kinetic, potential);
     if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::energy", rc);
@@ -343,6 +388,31 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
     sim.step(dt, nsteps, rebuild_every);
     sim.download(bodies);
 }
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, double G, double epsilon,
+                          TreeIntegrator integrator) {
+    if (bodies.empty()) return;
+    BarnesHutNewtonHip<D> sim(bodies, theta, -1, depth, far_order, G, epsilon);
+    if (integrator == TreeIntegrator::KickDriftKick) sim.step_kdk(dt, nsteps, rebuild_every); else sim.step(dt, nsteps, rebuild_every);
+    sim.download(bodies);
+}
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every,
+                                   int far_order, double G, double epsilon, TreeIntegrator integrator) {
+    check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_steps");
+    if (bodies.empty()) return;
+    BarnesHutNewtonHip<D> sim(bodies, theta, leaf_capacity, max_depth, far_order, G, epsilon);
+    if (integrator == TreeIntegrator::KickDriftKick) sim.step_kdk(dt, nsteps, rebuild_every); else sim.step(dt, nsteps, rebuild_every);
+    sim.download(bodies);
+}
+template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, TreeIntegrator);
+template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int, TreeIntegrator);
+template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int, TreeIntegrator);
+template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int, TreeIntegrator);
+template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, double, double, TreeIntegrator);
+template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int, double, double, TreeIntegrator);
+template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int, double, double, TreeIntegrator);
+template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int, double, double, TreeIntegrator);
 template std::vector<Vector<2>> barnes_hut_hip_n_body<2>(const std::vector<Body<2>>&, double, int, int, double, double);
 template std::vector<Vector<3>> barnes_hut_hip_n_body<3>(const std::vector<Body<3>>&, double, int, int, double, double);
 template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, double, double);

@@ -56,6 +56,9 @@ public:
     void evaluate(LeafLaw law, double G);
     // nsteps x { leaf sums; update_body_velocities; update_body_positions } (methods.cpp:425-450) on the device, asynchronous
     void step(LeafLaw law, double G, double dt, int nsteps);
+    // nsteps kick-drift-kick steps (nbx_leaf_plan_step_kdk; extension, second order): nsteps + 1 evaluations, positions and velocities at
+    // one time afterwards, asynchronous
+    void step_kdk(LeafLaw law, double G, double dt, int nsteps);
     void synchronize();   // waits for the steps queued so far
     void download(std::vector<Body<D>>& bodies);
     // 0 (NBX_FAR_MONOPOLE, every object's start) or 1 (NBX_FAR_QUADRUPOLE): the far cells' second-order term (nbx_leaf_plan_set_far_order)
@@ -118,6 +121,16 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
 template <int D>
 void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, std::size_t* n_leaves, std::size_t* largest_leaf);
 
+// The integrator of the step loops below.  KickDrift is the reference helpers' order and what every signature without an integrator
+// means; KickDriftKick is the synchronised second-order leapfrog (nbx_leaf_plan_step_octree_kdk: nsteps + 1 evaluations, the tree
+// built again before evaluation e when e % rebuild_every == 0, positions and velocities at one time afterwards).
+enum class TreeIntegrator { KickDrift, KickDriftKick };
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, TreeIntegrator integrator);
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every, int far_order,
+                                   TreeIntegrator integrator);
+
 // ---- softened Newtonian gravity through the tree (extension; NBX_LAW_NEWTON) ----
 // The four calls above under F_i = +G m_i sum_j m_j d / (r^2 + epsilon^2)^(3/2): the same trees, lists and far orders, with the
 // caller's G and a softening length epsilon > 0 (nbx_leaf_plan_set_softening).  Throw std::runtime_error on failure, epsilon = 0 included.
@@ -131,6 +144,12 @@ std::vector<Vector<D>> barnes_hut_hip_adaptive_n_body(const std::vector<Body<D>>
 template <int D>
 void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every,
                                    int far_order, double G, double epsilon);
+template <int D>
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, double G, double epsilon,
+                          TreeIntegrator integrator);
+template <int D>
+void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every,
+                                   int far_order, double G, double epsilon, TreeIntegrator integrator);
 
 // The same system kept on the device between chunks of steps: a context with the bodies and a plan with the octree built from them
 // (leaf_capacity < 0: fixed depth, depth 0 = barnes_hut_hip_depth; otherwise the adaptive tree down to `depth`).  energy() is the
@@ -147,6 +166,8 @@ public:
     BarnesHutNewtonHip& operator=(const BarnesHutNewtonHip&) = delete;
     std::vector<Vector<D>> forces();                          // of the bodies as they stand, on the tree as it stands
     void step(double dt, int nsteps, int rebuild_every = 1);  // nbx_leaf_plan_step_octree
+    void step_kdk(double dt, int nsteps, int rebuild_every = 1);   // nbx_leaf_plan_step_octree_kdk: kick-drift-kick, x and v at one time afterwards
+    double max_accel();                                       // largest |F_i| / m_i of the last evaluation (nbx_leaf_plan_max_accel); synchronises
     void energy(double* kinetic, double* potential);          // synchronises
     void tree_energy(double* kinetic, double* potential);     // synchronises
     void download(std::vector<Body<D>>& bodies);

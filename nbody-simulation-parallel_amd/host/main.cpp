@@ -294,6 +294,12 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
             << rel[rel.size() / 2] << ", 99th percentile " << rel[std::min(rel.size() - 1, rel.size() * 99 / 100)] << std::fixed
             << std::setprecision(6) << std::endl;
     };
+    // --integrator kdk: every `-m t` step loop below runs kick-drift-kick (nbx_leaf_plan_step_octree_kdk) and its rows carry `_kdk`;
+    // without it the loops, their names and their lines are kick-drift's alone
+    const bool tree_kdk = opt.integrator == "kdk";
+    const std::string kdk = tree_kdk ? "_kdk" : "";
+    const std::string kdk_words = tree_kdk ? " (kick-drift-kick)" : "";
+    const TreeIntegrator tree_integrator = tree_kdk ? TreeIntegrator::KickDriftKick : TreeIntegrator::KickDrift;
     for (int order = 0; order <= opt.far_order && m.find('t') != std::string::npos; ++order) {
         const std::string quad = order ? "_quad" : "";
         if (opt.leaf_cap > 0) {
@@ -320,17 +326,17 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                 if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive" + quad + ".f64", forces);
                 if (opt.steps > 0) {
                     std::vector<Body<D>> state = bodies;
-                    const long long step_us = safely_execute(log, "BarnesHut_HIP_adaptive_steps" + quad, [&] {
-                        barnes_hut_hip_adaptive_steps<D>(state, opt.theta, opt.leaf_cap, max_depth, opt.dt, opt.steps, 1, order);
+                    const long long step_us = safely_execute(log, "BarnesHut_HIP_adaptive_steps" + quad + kdk, [&] {
+                        barnes_hut_hip_adaptive_steps<D>(state, opt.theta, opt.leaf_cap, max_depth, opt.dt, opt.steps, 1, order, tree_integrator);
                         return 0;
                     });
                     if (step_us >= 0) {
-                        csv << "BarnesHut_HIP_adaptive_steps" << quad << "," << n << "," << D;
+                        csv << "BarnesHut_HIP_adaptive_steps" << quad << kdk << "," << n << "," << D;
                         write_time(csv, static_cast<double>(step_us) / 1e6);
                         csv << std::endl;
-                        out << "Barnes-Hut on HIP (adaptive), " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
+                        out << "Barnes-Hut on HIP (adaptive), " << opt.steps << " steps of dt " << opt.dt << kdk_words << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
                             << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
-                        if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive_steps" + quad + ".f64", state);
+                        if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive_steps" + quad + kdk + ".f64", state);
                     }
                 }
             }
@@ -354,9 +360,14 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                 if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP" + quad + ".f64", forces);
                 if (opt.steps > 0) {
                     std::vector<Body<D>> state = bodies;
-                    const long long step_us = safely_execute(log, "BarnesHut_HIP_steps" + quad, [&] { barnes_hut_hip_steps<D>(state, opt.theta, depth, opt.dt, opt.steps, 1, order); return 0; });
+                    const long long step_us = safely_execute(log, "BarnesHut_HIP_steps" + quad + kdk, [&] { barnes_hut_hip_steps<D>(state, opt.theta, depth, opt.dt, opt.steps, 1, order, tree_integrator); return 0; });
+                    if (step_us >= 0 && tree_kdk) {   // the kick-drift loop of this tree has never had a CSV row: its output stays as it is
+                        csv << "BarnesHut_HIP_steps" << quad << kdk << "," << n << "," << D;
+                        write_time(csv, static_cast<double>(step_us) / 1e6);
+                        csv << std::endl;
+                    }
                     if (step_us >= 0)
-                        out << "Barnes-Hut on HIP, " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
+                        out << "Barnes-Hut on HIP, " << opt.steps << " steps of dt " << opt.dt << kdk_words << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
                             << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
                 }
             }
@@ -420,7 +431,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                 if (!opt.dump.empty()) dump_raw(opt.dump + "_" + name + ".f64", forces);
                 if (opt.steps > 0) {
                     std::vector<Body<D>> state = bodies;
-                    const long long step_us = safely_execute(log, name + "_steps", [&] {
+                    const long long step_us = safely_execute(log, name + "_steps" + kdk, [&] {
                         BarnesHutNewtonHip<D> sim(bodies, opt.theta, capacity, depth, order, opt.G, opt.softening);
                         double ke = 0.0, pe = 0.0, e0 = 0.0, e0_tree = 0.0;
                         const int chunk = opt.energy_every > 0 ? opt.energy_every : opt.steps;
@@ -445,7 +456,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                         }
                         for (int done = 0; done < opt.steps;) {
                             const int k = std::min(chunk, opt.steps - done);
-                            sim.step(opt.dt, k, 1);
+                            if (tree_kdk) sim.step_kdk(opt.dt, k, 1); else sim.step(opt.dt, k, 1);   // kdk: x and v at one time, the energies synchronised
                             done += k;
                             if (opt.energy_every > 0) {
                                 sim.energy(&ke, &pe);
@@ -459,14 +470,14 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                         return 0;
                     });
                     if (step_us >= 0) {
-                        csv << name << "_steps," << n << "," << D;
+                        csv << name << "_steps" << kdk << "," << n << "," << D;
                         write_time(csv, static_cast<double>(step_us) / 1e6);
                         if (opt.accuracy) csv << ",";
                         csv << std::endl;
-                        out << "Barnes-Hut on HIP (Newtonian law), " << opt.steps << " steps of dt " << opt.dt << " rebuilding the tree every step: "
+                        out << "Barnes-Hut on HIP (Newtonian law), " << opt.steps << " steps of dt " << opt.dt << kdk_words << " rebuilding the tree every step: "
                             << static_cast<double>(step_us) / 1e6 << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps
                             << " ms per step, upload, download and energies included)" << std::endl;
-                        if (!opt.dump.empty()) dump_raw(opt.dump + "_" + name + "_steps.f64", state);
+                        if (!opt.dump.empty()) dump_raw(opt.dump + "_" + name + "_steps" + kdk + ".f64", state);
                     }
                 }
                 out << std::endl;
@@ -639,6 +650,7 @@ void usage(const char* argv0) {
               << "      --G <value>     Coupling constant of the stepping loop (default: the reference's 4.471e-21)" << std::endl
               << "      --integrator <kd|kdk> kd = update_body_velocities then update_body_positions per step (default, first order);" << std::endl
               << "                      kdk = the same helpers as a synchronised kick-drift-kick leapfrog (extension, second order)" << std::endl
+              << "                      with -m t: the tree's step loops run kick-drift-kick too and their rows carry _kdk" << std::endl
               << "      --law <reference|newton> Pair law of the stepping loop: the reference's r^-4 form (default) or the attractive" << std::endl
               << "                      softened Newtonian law (extension; needs --softening; Plummer velocities then use --G)" << std::endl
               << "                      with -m t: BarnesHut_HIP_newton rows behind the reference-law rows, judged against the all-pairs forces" << std::endl

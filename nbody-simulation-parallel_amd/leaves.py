@@ -589,3 +589,34 @@ def far_potentials(bodies: np.ndarray, dim: int, leaf_offsets, leaf_bodies, cell
         phi[ids] = term.sum(axis=1)
         S[ids] = np.abs(term).sum(axis=1)
     return phi, S
+
+
+# ---- the leapfrog through a plan: the fp64 specification of nbx_leaf_plan_step / _step_kdk (include/nbody_hip.h) ------------------
+
+def leapfrog_spec(bodies: np.ndarray, accel_fn, dt: float, nsteps: int, scheme: str = "kdk") -> np.ndarray:
+    """`nsteps` leapfrog steps of Body<D> rows (position[D], velocity[D], mass) in fp64 numpy; returns the new rows, `bodies` stays.
+    accel_fn(rows) -> a[n, D], the accelerations F_i / m_i of the rows as they stand, G and sign included -- an all-pairs sum, or
+    near_sums + far_sums through a structure, both fit.
+        scheme="kd":   nsteps x { a; v += a dt; x += v dt } -- the reference helpers' order (nbx_leaf_plan_step): first order, and
+                       v is half a step behind x in the second-order reading.
+        scheme="kdk":  a K(dt/2) D(dt) [ a K(dt) D(dt) ]^(nsteps-1) a K(dt/2), adjacent half-kicks merged into one multiply by dt
+                       (nbx_leaf_plan_step_kdk): nsteps + 1 evaluations, second order, time-reversible, x and v at one time."""
+    if scheme not in ("kd", "kdk"):
+        raise ValueError("scheme must be 'kd' or 'kdk'")
+    if nsteps < 0:
+        raise ValueError("nsteps must be >= 0")
+    b = np.array(bodies, dtype=np.float64, copy=True)
+    dim = (b.shape[1] - 1) // 2
+    x, v = b[:, :dim], b[:, dim:2 * dim]                         # views: accel_fn sees the rows as they stand
+    if nsteps == 0:
+        return b
+    if scheme == "kd":
+        for _ in range(nsteps):
+            v += np.asarray(accel_fn(b), dtype=np.float64) * dt
+            x += v * dt
+        return b
+    for e in range(nsteps + 1):
+        v += np.asarray(accel_fn(b), dtype=np.float64) * (0.5 * dt if e in (0, nsteps) else dt)
+        if e < nsteps:
+            x += v * dt
+    return b

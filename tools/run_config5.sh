@@ -15,6 +15,8 @@
 #   METHOD=tree ENERGY=tree LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # ... with an E_tree line behind every energy line:
 #                                              # the energy through the tree's own lists (--energy-tree) and the two potentials' difference
 # A run can be cut into segments where a job may not last 1000 steps (one GPU: 3.5 s per step):
+#   METHOD=tree INTEGRATOR=kdk LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # ... with kick-drift-kick through the tree
+#                                              # (nbx_leaf_plan_step_octree_kdk): step rows with `_kdk`, synchronised energies
 #   STEPS=250 DUMP=seg1 tools/run_config5.sh
 #   STEPS=250 LOAD=seg1_Leapfrog_HIP.f64 STEP_OFFSET=250 E0=<E of step 0> DUMP=seg2 tools/run_config5.sh   ... and so on;
 # k + k steps through a dump/load equal 2k steps bit for bit (tests/test_gpu_harness.py).  The state file is 56 B per body
@@ -46,7 +48,7 @@ fi
 if [ "$METHOD" = tree ]; then
     energy=()
     [ "$ENERGY" = tree ] && energy+=(--energy-tree)
-    ./nbody_sim -N "$N" -d 3 -m t --leaf-cap 32 --far-order 1 --init plummer --seed 5 --G "$G" --law "$LAW" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" ${energy[@]+"${energy[@]}"} | tee "$OUT"
+    ./nbody_sim -N "$N" -d 3 -m t --leaf-cap 32 --far-order 1 --init plummer --seed 5 --G "$G" --law "$LAW" --integrator "$INTEGRATOR" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" ${energy[@]+"${energy[@]}"} | tee "$OUT"
     grep -E "^step |Time taken|relative force error|ms per step" "$OUT" > "${OUT%.log}.summary.txt"
     echo "summary: ${OUT%.log}.summary.txt"
     exit 0
