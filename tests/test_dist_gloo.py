@@ -22,7 +22,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, n, dim, steps, dt, gscale, outdir):
+def _worker(rank, world, port, n, dim, steps, dt, gscale, outdir, case="generated"):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -32,7 +32,11 @@ def _worker(rank, world, port, n, dim, steps, dt, gscale, outdir):
         from cpu_shard_double import CpuShardDouble
         from oracle_lib import Oracle
         o = Oracle()
-        bodies = o.round_inputs_to_f32(o.generate(77, n, dim))
+        if case == "generated":
+            bodies = o.round_inputs_to_f32(o.generate(77, n, dim))
+        else:
+            from exchange_case import bodies_by_name
+            bodies = bodies_by_name(case, n, dim, world, 77)  # by name: "moving_pairs" (tests/exchange_case.py)
         pkg = nbody_amd.package
         layout = pkg.sharding.ShardLayout(n_total=n, n_shards=world, shard=rank, dim=dim)
         be = CpuShardDouble(bodies, layout)
@@ -82,12 +86,18 @@ def _worker(rank, world, port, n, dim, steps, dt, gscale, outdir):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,n,dim", [(2, 300, 3), (3, 301, 2), (2, 1, 3)])
-def test_sharded_steps_match_oracle(tmp_path, oracle, world, n, dim):
+@pytest.mark.parametrize("world,n,dim,case", [(2, 300, 3, "generated"), (3, 301, 2, "generated"), (2, 1, 3, "generated"),
+                                              (2, 300, 3, "moving_pairs"), (3, 301, 2, "moving_pairs")],
+                         ids=["2-300-3", "3-301-2", "2-1-3", "2-300-3-moving_pairs", "3-301-2-moving_pairs"])
+def test_sharded_steps_match_oracle(tmp_path, oracle, world, n, dim, case):
     import nbody_amd  # noqa: F401  (fails early if the package is broken)
     steps, dt, gscale = 4, 2.0, 1e24
-    mp.spawn(_worker, args=(world, _free_port(), n, dim, steps, dt, gscale, str(tmp_path)), nprocs=world, join=True)
-    bodies = oracle.round_inputs_to_f32(oracle.generate(77, n, dim))
+    mp.spawn(_worker, args=(world, _free_port(), n, dim, steps, dt, gscale, str(tmp_path), case), nprocs=world, join=True)
+    if case == "generated":
+        bodies = oracle.round_inputs_to_f32(oracle.generate(77, n, dim))
+    else:
+        from exchange_case import bodies_by_name
+        bodies = bodies_by_name(case, n, dim, world, 77)
     ref_f0 = oracle.brute_force_seq(bodies) * gscale
     # host loop from the oracle's leaves, forces taken on the fp32-rounded positions like the device path
     ref = bodies.copy()
@@ -136,7 +146,7 @@ def test_sharded_steps_match_oracle(tmp_path, oracle, world, n, dim):
     d = dim
     if n > 1:
         moved = np.abs(ref[:, d:2 * d] - bodies[:, d:2 * d]).max()
-        assert moved > 1e-6, "coupling too weak to detect a stale exchange"
+        assert moved > 1e-6, "coupling too weak to move the bodies measurably"
         assert np.allclose(finals[0][:, d:2 * d], ref[:, d:2 * d], rtol=0, atol=1e-7 * moved)
     assert np.allclose(finals[0][:, :d], ref[:, :d], rtol=1e-12, atol=0)
     assert np.array_equal(finals[0][:, -1], bodies[:, -1])

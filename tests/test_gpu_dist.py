@@ -24,16 +24,15 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, n, dim, steps, dt, gscale, outdir):
+def _worker(rank, world, port, n, dim, steps, dt, gscale, outdir, case="generated"):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         import nbody_amd as nbx
-        bodies = nbx.uniform_bodies(n, dim, 77)
-        bodies[:, :dim] = bodies[:, :dim].astype(np.float32)
-        bodies[:, -1] = bodies[:, -1].astype(np.float32)
+        from exchange_case import bodies_by_name
+        bodies = bodies_by_name(case, n, dim, world, 77)     # by name: "generated", or "moving_pairs" (tests/exchange_case.py)
         G = nbx.REFERENCE_G * gscale
         system = nbx.package.dist.make_hip_system(bodies, dim, rank=rank, world_size=world, device_index=0)
         system.compute_forces()
@@ -50,12 +49,20 @@ def _worker(rank, world, port, n, dim, steps, dt, gscale, outdir):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,n,dim", [(2, 6000, 3), (3, 5001, 2)])
-def test_two_ranks_one_gpu(tmp_path, oracle, world, n, dim):
+# moving_pairs: an input certified against a stale exchange between any two ranks (tests/test_exchange_case_cpu.py, cases
+# dist2 and dist3_2d); never more than three ranks on the one GPU
+@pytest.mark.parametrize("world,n,dim,case", [(2, 6000, 3, "generated"), (3, 5001, 2, "generated"),
+                                              (2, 1500, 3, "moving_pairs"), (3, 1027, 2, "moving_pairs")],
+                         ids=["2-6000-3", "3-5001-2", "2-1500-3-moving_pairs", "3-1027-2-moving_pairs"])
+def test_two_ranks_one_gpu(tmp_path, oracle, world, n, dim, case):
     from oracle_lib import assert_force_parity
     steps, dt, gscale = 3, 2.0, 1e24
-    mp.spawn(_worker, args=(world, _free_port(), n, dim, steps, dt, gscale, str(tmp_path)), nprocs=world, join=True)
-    bodies = oracle.round_inputs_to_f32(oracle.generate(77, n, dim))
+    mp.spawn(_worker, args=(world, _free_port(), n, dim, steps, dt, gscale, str(tmp_path), case), nprocs=world, join=True)
+    if case == "generated":
+        bodies = oracle.round_inputs_to_f32(oracle.generate(77, n, dim))
+    else:
+        from exchange_case import bodies_by_name
+        bodies = bodies_by_name(case, n, dim, world, 77)
     ref_f0 = oracle.brute_force_seq(bodies) * gscale
     S = oracle.force_magnitude_sums(bodies) * gscale
     ref = bodies.copy()
@@ -73,7 +80,7 @@ def test_two_ranks_one_gpu(tmp_path, oracle, world, n, dim):
         assert np.array_equal(fin, finals[0])
     d = dim
     moved = np.abs(ref[:, d:2 * d] - bodies[:, d:2 * d]).max()
-    assert moved > 1e-6
+    assert moved > 1e-6, "coupling too weak to move the bodies measurably"
     assert np.allclose(finals[0][:, d:2 * d], ref[:, d:2 * d], rtol=0, atol=3e-5 * moved)
     assert np.allclose(finals[0][:, :d], ref[:, :d], rtol=1e-9, atol=3e-5 * moved * dt * steps)
 

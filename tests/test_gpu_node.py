@@ -38,7 +38,7 @@ def test_virtual_ranks_forces_and_steps(nbx, oracle, ranks, n, dim):
         oracle.update_body_positions(cur, dt)
     d = dim
     moved = np.abs(cur[:, d:2 * d] - b[:, d:2 * d]).max()
-    assert moved > 1e-6, "coupling too weak to detect a stale exchange"
+    assert moved > 1e-6, "coupling too weak to move the bodies measurably"
     assert np.allclose(got[:, d:2 * d], cur[:, d:2 * d], rtol=0, atol=3e-5 * moved)
     assert np.allclose(got[:, :d], cur[:, :d], rtol=1e-9, atol=3e-5 * moved * dt * steps)
     r32 = oracle.round_inputs_to_f32(got)
