@@ -1,6 +1,7 @@
 // leaf_plan_api.hip -- the host side of the leaf-pair path behind the C ABI (include/nbody_hip.h): the one-shot call
 // nbx_leaf_pair_forces and the device-resident plan nbx_leaf_plan_*.  Validation, the choice of planner (leaf_plan.h on the host,
-// leaf_plan_device.h on the device), the octree built on the device (octree_device.h), and every entry point.  The kernels are
+// leaf_plan_device.h on the device), the octree built on the device (octree_device.h), and every entry point.  Every kick of
+// a plan is launch_kick_drift_slots (plan_kick, plan_enqueue_eval) and every stepping loop is plan_run_steps.  The kernels are
 // leaf_pair_kernel.hip's (through leaf_near.h), leaf_far_kernel.hip's (leaf_far.h) and, for the potential, leaf_phi_kernel.hip's
 // (leaf_phi.h); device memory is device_block.h's.
 #include "../../include/nbody_hip.h"
@@ -371,16 +372,9 @@ void ctx_bodies_moved(nbx_ctx* c) {
     c->tgt_cand_valid = 0; c->bad_list_pass = -1;
 }
 
-SlotKickArgs slot_kick_args(const nbx_leaf_plan* p, const nbx_ctx* c, double signedG, double dt) {
+SlotKickArgs slot_kick_args(const nbx_leaf_plan* p, const nbx_ctx* c, double signedG, double dt_kick, double dt_drift, bool drift) {
     SlotKickArgs k;
-    k.sums = p->sums; k.body_slot = p->body_slot; k.pslots = (uint32_t)p->pslots; k.dim = p->dim; k.pad = c->pad; k.count = c->count;
-    k.signedG = signedG; k.dt = dt; k.x64 = c->x64; k.v64 = c->v64; k.m64 = c->m64; k.pos_chunk = c->pos_all;
-    return k;
-}
-
-SlotKick2Args slot_kick2_args(const nbx_leaf_plan* p, const nbx_ctx* c, double signedG, double dt_kick, double dt_drift) {
-    SlotKick2Args k;
-    k.sums = p->sums; k.body_slot = p->body_slot; k.pslots = (uint32_t)p->pslots; k.dim = p->dim; k.pad = c->pad; k.count = c->count;
+    k.sums = p->sums; k.body_slot = p->body_slot; k.pslots = (uint32_t)p->pslots; k.dim = p->dim; k.pad = c->pad; k.drift = drift; k.count = c->count;
     k.signedG = signedG; k.dt_kick = dt_kick; k.dt_drift = dt_drift; k.x64 = c->x64; k.v64 = c->v64; k.m64 = c->m64; k.pos_chunk = c->pos_all;
     return k;
 }
@@ -420,6 +414,20 @@ int plan_check_law(const nbx_leaf_plan* p, int law, double mass_max) {
         if (mass_max > 0.0 && !(mass_max / eps3 > 1.0e-30)) return fail(NBX_ERR_INVALID, "softening too large for these masses: m / eps^3 underflows in fp32");
     }
     return NBX_OK;
+}
+
+// plan_check_law for host bodies about to be staged: one host pass over their masses under NBX_LAW_NEWTON (no other law pays for it)
+int plan_check_law_staged(const nbx_leaf_plan* p, int law, const void* bodies, size_t stride_bytes) {
+    if (law != NBX_LAW_NEWTON) return NBX_OK;
+    double mass_max = 0.0;
+    const char* const m0 = static_cast<const char*>(bodies) + 2 * (size_t)p->dim * sizeof(double);
+    for (size_t i = 0; i < p->n; ++i) {
+        double m;
+        std::memcpy(&m, m0 + i * stride_bytes, sizeof m);
+        m = std::fabs(m);
+        if (!(m <= mass_max)) mass_max = m;      // a NaN stays: refused by plan_check_law
+    }
+    return plan_check_law(p, law, mass_max);
 }
 
 // the near field: the pair kernels, which WRITE the slot-ordered sums
@@ -565,6 +573,17 @@ int create_plan_on_host(nbx_leaf_plan* p, const uint32_t* leaf_offsets, const ui
     return NBX_OK;
 }
 
+// What a new plan of either kind holds before it has a structure: its device made current (the caller's scope puts the old one
+// back), a stream from the parked pool, the pair kernels' two timing events and the event every piece of queued work is followed by.
+int plan_open(nbx_leaf_plan* p) {
+    NBX_HIP_TRY(hipSetDevice(p->device));
+    NBX_HIP_TRY(nbx::take_stream(p->device, &p->stream));
+    NBX_HIP_TRY(hipEventCreate(&p->ev0));
+    NBX_HIP_TRY(hipEventCreate(&p->ev1));
+    NBX_HIP_TRY(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+    return NBX_OK;
+}
+
 // nbx_leaf_plan_create and the one-shot call's plan: validation, the layout (device or host planner), the buffers an evaluation needs.
 int create_plan(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32_t* leaf_offsets, const uint32_t* leaf_bodies, size_t n_leaves,
                 const uint32_t* list_offsets, const uint32_t* list_sources, size_t forces_bytes) {
@@ -585,11 +604,7 @@ int create_plan(nbx_leaf_plan** out, int device, int dim, size_t n, const uint32
     PlanHolder hold(p);
     p->device = device; p->dim = dim; p->n = n; p->n_leaves = n_leaves;
     DeviceScope scope;
-    NBX_HIP_TRY(hipSetDevice(device));
-    NBX_HIP_TRY(nbx::take_stream(device, &p->stream));
-    NBX_HIP_TRY(hipEventCreate(&p->ev0));
-    NBX_HIP_TRY(hipEventCreate(&p->ev1));
-    NBX_HIP_TRY(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+    if ((rc = plan_open(p))) return rc;
     rc = on_device ? create_plan_on_device(p, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, slots, n_list, forces_bytes)
                    : create_plan_on_host(p, leaf_offsets, leaf_bodies, n_leaves, list_offsets, list_sources, forces_bytes);
     // the fresh sums: queued behind the layout, waited for by whoever evaluates first (plan_order_after_last)
@@ -725,12 +740,8 @@ int create_octree_plan(nbx_leaf_plan** out, nbx_ctx* c, int depth, size_t leaf_c
     p->octree = true; p->octree_depth = depth; p->octree_theta = theta; p->octree_capacity = leaf_capacity;
     p->tree_layout = nbx_octree::make_tree_layout(p->n, p->dim, depth, leaf_capacity > 0);
     DeviceScope scope;
-    hipError_t e = hipSetDevice(p->device);
-    if (e == hipSuccess) e = nbx::take_stream(p->device, &p->stream);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->done, hipEventDisableTiming);
-    const int rc = e == hipSuccess ? plan_build_octree(p, c) : nbx::fail_hip(e, "creating the plan", __FILE__, __LINE__);
+    int rc = plan_open(p);
+    if (!rc) rc = plan_build_octree(p, c);
     if (!rc) *out = hold.release();
     return rc;
 }
@@ -838,17 +849,7 @@ int nbx_leaf_plan_forces(nbx_leaf_plan* p, const void* bodies, size_t stride_byt
     if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
         return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
     if (int src = plan_needs_structure(p)) return src;
-    if (law == NBX_LAW_NEWTON) {   // one host pass over the masses about to be copied (no other law pays for it)
-        double mass_max = 0.0;
-        const char* const m0 = static_cast<const char*>(bodies) + 2 * (size_t)p->dim * sizeof(double);
-        for (size_t i = 0; i < p->n; ++i) {
-            double m;
-            std::memcpy(&m, m0 + i * stride_bytes, sizeof m);
-            m = std::fabs(m);
-            if (!(m <= mass_max)) mass_max = m;      // a NaN stays: refused below
-        }
-        if (int lrc = plan_check_law(p, law, mass_max)) return lrc;
-    }
+    if (int lrc = plan_check_law_staged(p, law, bodies, stride_bytes)) return lrc;
     hipStream_t s = p->stream;
     PlanScope in(p, s);
     if (in.rc) return in.rc;
@@ -911,26 +912,79 @@ int nbx_leaf_plan_get_forces(nbx_leaf_plan* p, double* forces_out) {
     return plan_mark_done(p, p->stream);
 }
 
-int nbx_leaf_plan_kick_drift(nbx_leaf_plan* p, nbx_ctx* c, double dt) {
+// ---- kicks and stepping loops (include/nbody_hip.h; "kick-drift-kick through a plan" for the _kdk and kick_drift2 entry points) ----
+// The kick of what the last evaluation left in the sums.  `drift` false is the pure kick, which leaves the positions -- and with
+// them the context's accelerations and lists -- valid; nbx_leaf_plan_kick_drift drifts for every dt, 0 included.
+static int plan_kick(nbx_leaf_plan* p, nbx_ctx* c, double dt_kick, double dt_drift, bool drift, const char* not_evaluated) {
     if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (!p->evaluated) return fail(NBX_ERR_STATE, "evaluate the leaf sums before kick_drift");
+    if (!p->evaluated) return fail(NBX_ERR_STATE, not_evaluated);
     if (int crc = plan_check_ctx(p, c, false)) return crc;
     if (p->last_ctx_id != c->id) return fail(NBX_ERR_STATE, "the last evaluation was not made from this context");
     hipStream_t s = c->stream;
     PlanScope in(p, s);
     if (in.rc) return in.rc;
-    NBX_HIP_TRY(launch_kick_drift_slots(slot_kick_args(p, c, p->last_signedG, dt), s));
-    ctx_bodies_moved(c);
+    NBX_HIP_TRY(launch_kick_drift_slots(slot_kick_args(p, c, p->last_signedG, dt_kick, dt_drift, drift), s));
+    if (drift) ctx_bodies_moved(c);
     return plan_mark_done(p, s);
 }
 
-// one step's device work on stream s, nothing else (no events, no waits)
-static int plan_enqueue_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double signedG, double dt, hipStream_t s) {
+int nbx_leaf_plan_kick_drift(nbx_leaf_plan* p, nbx_ctx* c, double dt) {
+    return plan_kick(p, c, dt, dt, true, "evaluate the leaf sums before kick_drift");
+}
+
+int nbx_leaf_plan_kick_drift2(nbx_leaf_plan* p, nbx_ctx* c, double dt_kick, double dt_drift) {
+    return plan_kick(p, c, dt_kick, dt_drift, dt_drift != 0.0, "evaluate the leaf sums before kick_drift2");
+}
+
+// one evaluation's device work on stream s and the kick (and drift) behind it, nothing else (no events, no waits)
+static int plan_enqueue_eval(nbx_leaf_plan* p, nbx_ctx* c, int law, double signedG, double dt_kick, double dt_drift, bool drift, hipStream_t s) {
     NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
     if (int rc = plan_gather_resident(p, c, s)) return rc;
     if (int rc = plan_launch_pairs(p, law, s, false)) return rc;
-    NBX_HIP_TRY(launch_kick_drift_slots(slot_kick_args(p, c, signedG, dt), s));
+    NBX_HIP_TRY(launch_kick_drift_slots(slot_kick_args(p, c, signedG, dt_kick, dt_drift, drift), s));
     return NBX_OK;
+}
+
+enum class Scheme { KickDrift, KickDriftKick };
+
+// Every stepping loop, behind its entry point's argument checks.  Kick-drift is nsteps evaluations, each followed by a kick and a
+// drift by dt.  Kick-drift-kick is F K(dt/2) D(dt) [F K(dt) D(dt)]^(n-1) F K(dt/2), evaluations 0 .. nsteps with the adjacent
+// half-kicks merged into one multiply by dt (nbx_ctx_step_kdk's form); its kicks are nbx_leaf_plan_kick_drift2's, for which a
+// drift by 0 is the pure kick.  rebuild_every > 0 rebuilds the plan's octree before every rebuild_every-th evaluation.
+static int plan_run_steps(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every, Scheme scheme) {
+    if (nsteps == 0) return NBX_OK;
+    const bool rebuilds = rebuild_every > 0;   // evaluation 0 rebuilds: what the last build left does not matter
+    if (!rebuilds)
+        if (int src = plan_needs_structure(p)) return src;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
+    hipStream_t s = c->stream;
+    PlanScope in(p, s);
+    if (in.rc) return in.rc;
+    const double signedG = signed_G(law, G);
+    const bool kdk = scheme == Scheme::KickDriftKick;
+    // Plain launches, queued ahead of the device: a step is GPU-bound (0.36 ms of kernels at N = 2^20; 5 launches cost the host
+    // ~25 us).  A captured HIP graph was measured: 8-15 ms to capture and instantiate, then the same 72.4 ms per 200 steps at
+    // N = 2^20 and 7.97 against 8.39 ms at N = 20,000 -- it would need thousands of steps to pay for itself (tools/time_leaf_steps.py).
+    // The bookkeeping is done once behind the loop, unless the loop rebuilds: then a later evaluation can leave early (a refused
+    // build) and plan_build_octree orders itself behind `done`, so every evaluation is recorded as it is queued.
+    auto queued = [&](bool drifted) {   // the bookkeeping behind evaluations queued on s
+        plan_record_evaluation(p, law, signedG, c);
+        if (drifted) ctx_bodies_moved(c);
+        return plan_mark_done(p, s);
+    };
+    for (int e = 0; e < nsteps + (kdk ? 1 : 0); ++e) {
+        if (rebuilds) {
+            int rc = e % rebuild_every == 0 ? plan_build_octree(p, c) : NBX_OK;
+            if (!rc) rc = plan_needs_structure(p);
+            if (rc) return rc;
+        }
+        const bool closing = kdk && e == nsteps;            // the closing half-kick: no drift behind it
+        const double dt_kick = kdk && (e == 0 || closing) ? 0.5 * dt : dt, dt_drift = closing ? 0.0 : dt;
+        if (int rc = plan_enqueue_eval(p, c, law, signedG, dt_kick, dt_drift, !kdk || dt_drift != 0.0, s)) return rc;
+        if (rebuilds)
+            if (int rc = queued(!closing)) return rc;
+    }
+    return rebuilds ? NBX_OK : queued(true);
 }
 
 int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps) {
@@ -938,70 +992,7 @@ int nbx_leaf_plan_step(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double d
     if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if (nsteps < 0) return fail(NBX_ERR_INVALID, "nsteps must be >= 0");
     if (int crc = plan_check_ctx(p, c)) return crc;
-    if (nsteps == 0) return NBX_OK;
-    if (int src = plan_needs_structure(p)) return src;
-    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
-    hipStream_t s = c->stream;
-    PlanScope in(p, s);
-    if (in.rc) return in.rc;
-    const double signedG = signed_G(law, G);
-    // Plain launches, queued ahead of the device: a step is GPU-bound (0.36 ms of kernels at N = 2^20; 5 launches cost the host
-    // ~25 us).  A captured HIP graph was measured: 8-15 ms to capture and instantiate, then the same 72.4 ms per 200 steps at
-    // N = 2^20 and 7.97 against 8.39 ms at N = 20,000 -- it would need thousands of steps to pay for itself (tools/time_leaf_steps.py).
-    for (int k = 0; k < nsteps; ++k)
-        if (int rc = plan_enqueue_step(p, c, law, signedG, dt, s)) return rc;
-    plan_record_evaluation(p, law, signedG, c);
-    ctx_bodies_moved(c);
-    return plan_mark_done(p, s);
-}
-
-int nbx_leaf_plan_step_octree(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
-    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
-    if (nsteps < 0 || rebuild_every < 0) return fail(NBX_ERR_INVALID, "nsteps and rebuild_every must be >= 0");
-    if (int rc = plan_check_ctx(p, c)) return rc;
-    if (rebuild_every > 0 && !p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
-    if (nsteps == 0) return NBX_OK;
-    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
-    hipStream_t s = c->stream;
-    PlanScope in(p, s);
-    if (in.rc) return in.rc;
-    const double signedG = signed_G(law, G);
-    for (int k = 0; k < nsteps; ++k) {
-        int rc = rebuild_every > 0 && k % rebuild_every == 0 ? plan_build_octree(p, c) : NBX_OK;
-        if (!rc) rc = plan_needs_structure(p);
-        if (!rc) rc = plan_enqueue_step(p, c, law, signedG, dt, s);
-        if (rc) return rc;
-        plan_record_evaluation(p, law, signedG, c);
-        ctx_bodies_moved(c);
-        if ((rc = plan_mark_done(p, s))) return rc;
-    }
-    return NBX_OK;
-}
-
-// ---- kick-drift-kick (include/nbody_hip.h "kick-drift-kick through a plan") ---------------------------------------------------
-int nbx_leaf_plan_kick_drift2(nbx_leaf_plan* p, nbx_ctx* c, double dt_kick, double dt_drift) {
-    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
-    if (!p->evaluated) return fail(NBX_ERR_STATE, "evaluate the leaf sums before kick_drift2");
-    if (int crc = plan_check_ctx(p, c, false)) return crc;
-    if (p->last_ctx_id != c->id) return fail(NBX_ERR_STATE, "the last evaluation was not made from this context");
-    hipStream_t s = c->stream;
-    PlanScope in(p, s);
-    if (in.rc) return in.rc;
-    NBX_HIP_TRY(launch_kick_drift_slots2(slot_kick2_args(p, c, p->last_signedG, dt_kick, dt_drift), s));
-    if (dt_drift != 0.0) ctx_bodies_moved(c);   // a pure kick leaves the positions -- and with them the context's accelerations and lists -- valid
-    return plan_mark_done(p, s);
-}
-
-// evaluation number e of 0 .. nsteps and the kick (and drift) behind it: F K(dt/2) D(dt) [F K(dt) D(dt)]^(n-1) F K(dt/2), the
-// adjacent half-kicks merged into one multiply by dt (nbx_ctx_step_kdk's form)
-static int plan_enqueue_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double signedG, double dt, int e, int nsteps, hipStream_t s) {
-    NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
-    if (int rc = plan_gather_resident(p, c, s)) return rc;
-    if (int rc = plan_launch_pairs(p, law, s, false)) return rc;
-    const double dt_kick = e == 0 || e == nsteps ? 0.5 * dt : dt;
-    NBX_HIP_TRY(launch_kick_drift_slots2(slot_kick2_args(p, c, signedG, dt_kick, e < nsteps ? dt : 0.0), s));
-    return NBX_OK;
+    return plan_run_steps(p, c, law, G, dt, nsteps, 0, Scheme::KickDrift);
 }
 
 int nbx_leaf_plan_step_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps) {
@@ -1009,42 +1000,27 @@ int nbx_leaf_plan_step_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, doub
     if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if (nsteps < 0) return fail(NBX_ERR_INVALID, "nsteps must be >= 0");
     if (int crc = plan_check_ctx(p, c)) return crc;
-    if (nsteps == 0) return NBX_OK;
-    if (int src = plan_needs_structure(p)) return src;
-    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
-    hipStream_t s = c->stream;
-    PlanScope in(p, s);
-    if (in.rc) return in.rc;
-    const double signedG = signed_G(law, G);
-    for (int e = 0; e <= nsteps; ++e)
-        if (int rc = plan_enqueue_kdk(p, c, law, signedG, dt, e, nsteps, s)) return rc;
-    plan_record_evaluation(p, law, signedG, c);
-    ctx_bodies_moved(c);
-    return plan_mark_done(p, s);
+    return plan_run_steps(p, c, law, G, dt, nsteps, 0, Scheme::KickDriftKick);
 }
 
-int nbx_leaf_plan_step_octree_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
+// what the two octree loops check before plan_run_steps
+static int check_octree_steps(const nbx_leaf_plan* p, const nbx_ctx* c, int law, int nsteps, int rebuild_every) {
     if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
     if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
     if (nsteps < 0 || rebuild_every < 0) return fail(NBX_ERR_INVALID, "nsteps and rebuild_every must be >= 0");
     if (int rc = plan_check_ctx(p, c)) return rc;
     if (rebuild_every > 0 && !p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
-    if (nsteps == 0) return NBX_OK;
-    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
-    hipStream_t s = c->stream;
-    PlanScope in(p, s);
-    if (in.rc) return in.rc;
-    const double signedG = signed_G(law, G);
-    for (int e = 0; e <= nsteps; ++e) {
-        int rc = rebuild_every > 0 && e % rebuild_every == 0 ? plan_build_octree(p, c) : NBX_OK;
-        if (!rc) rc = plan_needs_structure(p);
-        if (!rc) rc = plan_enqueue_kdk(p, c, law, signedG, dt, e, nsteps, s);
-        if (rc) return rc;
-        plan_record_evaluation(p, law, signedG, c);
-        if (e < nsteps) ctx_bodies_moved(c);
-        if ((rc = plan_mark_done(p, s))) return rc;
-    }
     return NBX_OK;
+}
+
+int nbx_leaf_plan_step_octree(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
+    if (int rc = check_octree_steps(p, c, law, nsteps, rebuild_every)) return rc;
+    return plan_run_steps(p, c, law, G, dt, nsteps, rebuild_every, Scheme::KickDrift);
+}
+
+int nbx_leaf_plan_step_octree_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
+    if (int rc = check_octree_steps(p, c, law, nsteps, rebuild_every)) return rc;
+    return plan_run_steps(p, c, law, G, dt, nsteps, rebuild_every, Scheme::KickDriftKick);
 }
 
 // An observer like the potential calls: it reads the slot sums and the inverse map and writes its own 8-byte word.
@@ -1296,17 +1272,7 @@ int nbx_leaf_plan_potentials(nbx_leaf_plan* p, const void* bodies, size_t stride
     if (stride_bytes < min_stride || stride_bytes % sizeof(double) != 0)
         return fail(NBX_ERR_INVALID, "body stride must be a multiple of 8 and >= sizeof(Body<dim>)");
     if (int src = plan_needs_structure(p)) return src;
-    if (law == NBX_LAW_NEWTON) {   // one host pass over the masses about to be copied, as in nbx_leaf_plan_forces
-        double mass_max = 0.0;
-        const char* const m0 = static_cast<const char*>(bodies) + 2 * (size_t)p->dim * sizeof(double);
-        for (size_t i = 0; i < p->n; ++i) {
-            double m;
-            std::memcpy(&m, m0 + i * stride_bytes, sizeof m);
-            m = std::fabs(m);
-            if (!(m <= mass_max)) mass_max = m;      // a NaN stays: refused below
-        }
-        if (int lrc = plan_check_law(p, law, mass_max)) return lrc;
-    }
+    if (int lrc = plan_check_law_staged(p, law, bodies, stride_bytes)) return lrc;
     hipStream_t s = p->stream;
     PlanScope in(p, s);
     if (in.rc) return in.rc;

@@ -253,32 +253,24 @@ struct KickDriftArgs {
 };
 hipError_t launch_kick_drift(const KickDriftArgs& k, hipStream_t stream);
 // The same update from fp64 leaf sums indexed by padded slot (leaf plan, leaf_plan_api.hip): body l's sum is
-// sums[k][body_slot[l]] (0 when body_slot[l] == 0xffffffff: the body belongs to no leaf); F = (signedG m) sum.
+// sums[k][body_slot[l]] (0 when body_slot[l] == 0xffffffff: the body belongs to no leaf); F = (signedG m) sum.  The caller says
+// whether the drift runs: `drift` false launches the pure kick, which touches no position, while a drift by dt_drift = 0 still
+// reads and writes them.
 struct SlotKickArgs {
     const double* sums;        // [dim][pslots]
     const uint32_t* body_slot; // [count]
     uint32_t pslots;
     int dim;
     unsigned pad;
+    bool drift;                // host side only (it picks the kernel); it lies in the padding in front of `count`
     size_t count;
-    double signedG, dt;
+    double signedG, dt_kick, dt_drift;   // as KickDriftArgs': both = dt is the reference's kick then drift
     double* x64; double* v64; const double* m64;
     float* pos_chunk;
 };
+static_assert(offsetof(SlotKickArgs, drift) == 28 && offsetof(SlotKickArgs, count) == 32 && sizeof(SlotKickArgs) == 96,
+              "SlotKickArgs::drift must stay inside the padding: the kernels' argument block is the one they were compiled for");
 hipError_t launch_kick_drift_slots(const SlotKickArgs& k, hipStream_t stream);
-// the same with the kick's and the drift's step apart; dt_drift == 0 launches the pure kick, which touches no position
-struct SlotKick2Args {
-    const double* sums;        // [dim][pslots]
-    const uint32_t* body_slot; // [count]
-    uint32_t pslots;
-    int dim;
-    unsigned pad;
-    size_t count;
-    double signedG, dt_kick, dt_drift;
-    double* x64; double* v64; const double* m64;
-    float* pos_chunk;
-};
-hipError_t launch_kick_drift_slots2(const SlotKick2Args& k, hipStream_t stream);
 // *out (device, 8 bytes; zeroed here first) = bit pattern of max over the n bodies with a slot of absG * |sums[.][slot]|, fp64
 hipError_t launch_slot_accel_max(const double* sums, const uint32_t* body_slot, uint32_t pslots, int dim, size_t n, double absG,
                                  unsigned long long* out, hipStream_t stream);

@@ -95,30 +95,13 @@ __global__ __launch_bounds__(256) void kick_drift_kernel(KickDriftArgs a) {
     a.pos_chunk[(size_t)k * a.pad + l] = (float)x;
 }
 
-// The leaf plan's stepping loop: the same two helpers fed the near-field sums of the tree codes (fp64, per padded slot).
-__global__ __launch_bounds__(256) void kick_drift_slots_kernel(SlotKickArgs a) {
-    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (l >= a.count) return;
-    const int k = (int)blockIdx.y;
-    const double m = a.m64[l];
-    const uint32_t slot = a.body_slot[l];
-    const double sum = slot == 0xffffffffu ? 0.0 : a.sums[(size_t)k * a.pslots + slot];
-    const double F = (a.signedG * m) * sum;
-    double v = a.v64[(size_t)k * a.pad + l];
-    double x = a.x64[(size_t)k * a.pad + l];
-    v += (F / m) * a.dt;
-    x += v * a.dt;
-    a.v64[(size_t)k * a.pad + l] = v;
-    a.x64[(size_t)k * a.pad + l] = x;
-    a.pos_chunk[(size_t)k * a.pad + l] = (float)x;
-}
-
-// The same kernel with the kick's and the drift's step apart -- the building block of kick-drift-kick through a plan.  The expressions
-// and their order are kick_drift_slots_kernel's, so dt_kick == dt_drift gives its bits (this file is built without contraction: each
-// multiply and each add rounds by itself, there and here).  DRIFT = false is a pure kick: x64 and the fp32 position chunk are neither read nor written, so a velocity that is not
-// finite cannot reach a position through inf * 0.
+// The leaf plan's kick and drift, every stepping loop's and kick-drift-kick's building block: kick_drift_kernel's two helpers fed the
+// near-field sums of the tree codes (fp64, per padded slot), the kick's and the drift's step apart as there.  dt_kick == dt_drift is
+// the reference's kick then drift (this file is built without contraction: each multiply and each add rounds by itself).  DRIFT =
+// false is a pure kick: x64 and the fp32 position chunk are neither read nor written, so a velocity that is not finite cannot reach
+// a position through inf * 0.
 template <bool DRIFT>
-__global__ __launch_bounds__(256) void kick_drift_slots2_kernel(SlotKick2Args a) {
+__global__ __launch_bounds__(256) void kick_drift_slots_kernel(SlotKickArgs a) {
     const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (l >= a.count) return;
     const int k = (int)blockIdx.y;
@@ -279,15 +262,9 @@ hipError_t launch_kick_drift(const KickDriftArgs& k, hipStream_t stream) {
 
 hipError_t launch_kick_drift_slots(const SlotKickArgs& k, hipStream_t stream) {
     if (k.count == 0) return hipSuccess;
-    hipLaunchKernelGGL(kick_drift_slots_kernel, dim3(blocks_for(k.count), (unsigned)k.dim, 1), dim3(256), 0, stream, k);
-    return hipGetLastError();
-}
-
-hipError_t launch_kick_drift_slots2(const SlotKick2Args& k, hipStream_t stream) {
-    if (k.count == 0) return hipSuccess;
     const dim3 grid(blocks_for(k.count), (unsigned)k.dim, 1);
-    if (k.dt_drift != 0.0) hipLaunchKernelGGL(kick_drift_slots2_kernel<true>, grid, dim3(256), 0, stream, k);
-    else hipLaunchKernelGGL(kick_drift_slots2_kernel<false>, grid, dim3(256), 0, stream, k);
+    if (k.drift) hipLaunchKernelGGL(kick_drift_slots_kernel<true>, grid, dim3(256), 0, stream, k);
+    else hipLaunchKernelGGL(kick_drift_slots_kernel<false>, grid, dim3(256), 0, stream, k);
     return hipGetLastError();
 }
 

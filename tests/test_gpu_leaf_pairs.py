@@ -329,6 +329,14 @@ def test_invalid_structures_are_rejected_before_any_launch(nbx, oracle):
             c.upload(b)
             plan.forces_ctx(c)                                      # a sharded context
     assert nbx.leaf_pair_forces_hip(np.zeros((0, 7)), np.array([0]), np.zeros(0), np.array([0]), np.zeros(0)).shape == (0, 3)
+    # bodies, but no leaf holds one (two empty leaves; no leaf at all): no error, and exactly zero for every body
+    nothing = ((np.array([0, 0, 0]), np.zeros(0), np.array([0, 1, 2]), np.array([0, 1])), (np.array([0]), np.zeros(0), np.array([0]), np.zeros(0)))
+    for leaves in nothing:
+        for which in ("host", "device"):
+            with planner(which):
+                with nbx.LeafPlan(10, 3, *leaves) as plan:
+                    for f in (nbx.leaf_pair_forces_hip(b, *leaves), plan.forces(b)):
+                        assert f.shape == (10, 3) and np.array_equal(f, np.zeros((10, 3))) and not np.signbit(f).any()
 
 
 def test_a_plan_names_its_context_by_identity_not_by_address(nbx, oracle):

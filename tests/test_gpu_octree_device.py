@@ -288,6 +288,17 @@ def test_refusals(nbx, oracle):
             c.upload(bad)
             refused(NBX_ERR_INVALID, lambda: plan.rebuild(c))
             refused(NBX_ERR_STATE, lambda: plan.forces_ctx(c, 1, oracle.G))
+            # rebuild_every = 0 is step / step_kdk: of the two refusals that hold here (no structure, and for NBX_LAW_NEWTON no
+            # softening length) every loop reports the one step reports -- the same status, the same words.  Both refusals are
+            # NBX_ERR_STATE, so it is the words below, not the status, that tell a loop checking the law first from one that does not
+            said = []
+            for loop in (lambda: plan.step(c, nbx.LAW_NEWTON, oracle.G, 1.0, 1), lambda: plan.step_octree(c, nbx.LAW_NEWTON, oracle.G, 1.0, 1, 0),
+                         lambda: plan.step_kdk(c, nbx.LAW_NEWTON, oracle.G, 1.0, 1), lambda: plan.step_octree_kdk(c, nbx.LAW_NEWTON, oracle.G, 1.0, 1, 0)):
+                with pytest.raises(nbx.NbxError) as e:
+                    loop()
+                assert e.value.status == NBX_ERR_STATE, str(e.value)
+                said.append(str(e.value).split(" -- ", 1)[1])
+            assert "octree build was refused" in said[0] and said.count(said[0]) == 4, said
             c.upload(b)
             plan.rebuild(c)
             assert_same_structure(plan.structure(), want, "rebuilt after a refused rebuild")

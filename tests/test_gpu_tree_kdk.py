@@ -1,5 +1,5 @@
 """GPU: kick-drift-kick through a leaf plan -- nbx_leaf_plan_kick_drift2, _step_kdk, _step_octree_kdk and _max_accel
-(csrc/state_kernels.hip: kick_drift_slots2_kernel, slot_accel_max_kernel; csrc/leaf_plan_api.hip) through the C ABI.
+(csrc/state_kernels.hip: kick_drift_slots_kernel, slot_accel_max_kernel; csrc/leaf_plan_api.hip) through the C ABI.
 
 Inputs, unless a test says otherwise, are those of tests/test_gpu_newton_tree.py::test_stepping: 20,000 generated bodies, an octree of
 depth 3 at theta 0.5 built on the device, far order 1, EPS = 32768, G = oracle.G * 1e24, dt = 1.5.  What is judged bit for bit is
@@ -76,6 +76,28 @@ def test_equal_steps_give_the_bits_of_kick_drift(nbx, oracle, n, law):
     assert not np.array_equal(ga[:, :dim], b0[:, :dim])
     if n > 1:
         assert not np.array_equal(ga[:, dim:2 * dim], b0[:, dim:2 * dim]), "coupling too weak to test anything"
+
+
+@pytest.mark.parametrize("n", (257, 1))
+def test_a_zero_step_of_kick_drift_changes_nothing(nbx, oracle, n):
+    """kick_drift(0) runs the drifting kernel like every other step (it reads and writes the positions): the bodies downloaded are
+    the uploaded bits, and a following kick_drift2(dt, dt) gives the bits of the same call on a second plan and context that
+    skipped the zero step."""
+    dim = 3
+    b0 = bodies_of(oracle, dim, n)
+    G = oracle.G * 1e26
+    with nbx.Context(n, dim) as ca, nbx.Context(n, dim) as cb:
+        ca.upload(b0); cb.upload(b0)
+        with nbx.LeafPlan(n, dim, *nbx.leaves.all_pairs_leaves(n, 64)) as pa, nbx.LeafPlan(n, dim, *nbx.leaves.all_pairs_leaves(n, 64)) as pb:
+            pa.forces_ctx(ca, nbx.LAW_TREE_LEAF, G, fetch=False)
+            pa.kick_drift(ca, 0.0)
+            assert np.array_equal(downloaded(ca, b0), b0)
+            pa.kick_drift2(ca, DT, DT)
+            pb.forces_ctx(cb, nbx.LAW_TREE_LEAF, G, fetch=False)
+            pb.kick_drift2(cb, DT, DT)
+            ga, gb = downloaded(ca, b0), downloaded(cb, b0)
+    assert np.array_equal(ga, gb)
+    assert not np.array_equal(ga[:, :dim], b0[:, :dim])
 
 
 # ---- 2: unequal steps against the oracle's helpers ------------------------------------------------------------------------------
