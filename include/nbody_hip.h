@@ -367,6 +367,56 @@ int nbx_leaf_plan_step_octree_kdk(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, do
  * rebuild without one) and when the context of the last evaluation no longer exists. */
 int nbx_leaf_plan_max_accel(nbx_leaf_plan* plan, double* a_max);
 
+/* ---- kick-drift-kick with the step chosen on the device -------------------------------------------------------------------------
+ * nbx_leaf_plan_step_kdk_adaptive: the kick-drift-kick loop above with every step's size chosen ON THE DEVICE from the evaluation
+ * just made (nbx_leaf_plan_max_accel's value of its sums); nothing is read back to choose it.  The rule, in fp64:
+ *       t = t_start; prev = 0; steps = 0
+ *       for e = 0, 1, 2, ...:
+ *           rebuild the octree when rebuild_every > 0 and e % rebuild_every == 0   (as nbx_leaf_plan_step_octree_kdk)
+ *           evaluate (nbx_leaf_plan_forces_ctx(NULL, NULL)); a_max = nbx_leaf_plan_max_accel's value for these sums
+ *           if a_max is not finite: status = 1; stop                               (no kick is made with these sums)
+ *           if t >= t_end or steps == max_steps:                                   the closing half-kick
+ *               v += (F / m) (0.5 prev); record (a_max, 0); stop
+ *           dt = choose(a_max);  if dt >= t_end - t: dt = t_end - t, t = t_end  else t = t + dt
+ *           v += (F / m) (0.5 prev + 0.5 dt);  x += v dt;  prev = dt;  steps += 1;  record (a_max, dt)
+ * choose(a_max): raw = sqrt(accel_length / a_max), +infinity when a_max == 0.  pow2 == 0: min(max(raw, dt_min), dt_max).
+ * pow2 == 1: d = dt_max; while (d > raw && 0.5 d >= dt_min) d = 0.5 d -- the halvings are exact, so every dt is dt_max 2^-j.  Only
+ * the step that lands on t_end may be shorter than dt_min.
+ * The kicks are nbx_leaf_plan_kick_drift2's arithmetic: a caller who replays the recorded dt's with _forces_ctx and
+ * _kick_drift2(0.5 prev + 0.5 dt, dt), then the closing _kick_drift2(0.5 prev, 0), gets the same bits.  A closing kick with
+ * prev == 0 is not applied, and no kick is applied once the loop has stopped.
+ * TIME LEVELS: afterwards x and v are BOTH at the clock's t and the plan holds the sums of the final positions -- unless
+ * status == 1: then the loop stopped before the kick of the evaluation whose a_max was not finite, x is at t and v is HALF A STEP
+ * (0.5 dt_last) BEHIND it.  Far order and softening survive; the potential calls remain observers; max_steps == 0 does nothing.
+ * With rebuild_every == 0 the call is asynchronous and reads nothing back: the host cannot know when t_end is reached, so it queues
+ * evaluations up to number max_steps; those behind the stop find the positions unmoved, give the same sums, record nothing and kick
+ * nothing.  (The loop stops queueing early once a copy it makes anyway has shown it the stop; the results are the same.)
+ * Refusals, before anything is launched.  NBX_ERR_INVALID: a null argument, an unknown law, a control outside the ranges given
+ * with its fields, reserved != 0, max_steps < 0 or > 1 << 20, rebuild_every < 0 (all of these need no device), the wrong context.
+ * NBX_ERR_STATE: rebuild_every > 0 on a plan not made by nbx_leaf_plan_create_octree; NBX_LAW_NEWTON while the softening is 0.
+ *
+ * nbx_leaf_plan_get_step_clock: where the last adaptive call left the device's clock; synchronises.  NBX_ERR_STATE before the
+ * first adaptive call on the plan.  evaluations counts those the rule above acted on (the one that stopped it included).
+ * nbx_leaf_plan_get_step_history: the (a_max, dt) pairs recorded by the last adaptive call, oldest first: *count is how many there
+ * are, and min(capacity, *count) of them are written (either array may be null).  The closing evaluation's entry has dt = 0. */
+typedef struct nbx_step_control {
+    double accel_length;    /* c > 0, finite: dt_raw = sqrt(c / a_max); c = eta^2 * epsilon is the usual choice */
+    double dt_min, dt_max;  /* 0 < dt_min <= dt_max, finite */
+    double t_start, t_end;  /* t_start finite; t_end finite or +infinity, not NaN */
+    int    pow2;            /* 0: dt = clamp(dt_raw, dt_min, dt_max); 1: dt = dt_max / 2^j (rule above) */
+    int    reserved;        /* must be 0 */
+} nbx_step_control;
+typedef struct nbx_step_clock {
+    double t, dt_last, a_max_last;
+    uint32_t steps, evaluations;
+    int finished;           /* 1: t reached t_end */
+    int status;             /* 0 ok; 1: an a_max was not finite, the loop stopped before kicking with it */
+} nbx_step_clock;
+int nbx_leaf_plan_step_kdk_adaptive(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, const nbx_step_control* control, int max_steps,
+                                    int rebuild_every);
+int nbx_leaf_plan_get_step_clock(nbx_leaf_plan* plan, nbx_step_clock* clock);
+int nbx_leaf_plan_get_step_history(nbx_leaf_plan* plan, double* a_max_out, double* dt_out, size_t capacity, size_t* count);
+
 /* ---- the potential through a plan -------------------------------------------------------------------------------------------
  * What the plan's sums are the gradient of, through the same near lists and far cells, in O(list length) like the forces.  Per unit
  * G m_i, body i of target leaf t has

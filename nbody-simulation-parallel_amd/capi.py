@@ -68,6 +68,9 @@ ABI = [
     ("nbx_leaf_plan_step_kdk", _i, [_vp, _vp, _i, _d, _d, _i]),
     ("nbx_leaf_plan_step_octree_kdk", _i, [_vp, _vp, _i, _d, _d, _i, _i]),
     ("nbx_leaf_plan_max_accel", _i, [_vp, _pd]),
+    ("nbx_leaf_plan_step_kdk_adaptive", _i, [_vp, _vp, _i, _d, _vp, _i, _i]),
+    ("nbx_leaf_plan_get_step_clock", _i, [_vp, _vp]),
+    ("nbx_leaf_plan_get_step_history", _i, [_vp, _vp, _vp, _sz, _c.POINTER(_sz)]),
     ("nbx_leaf_plan_potentials", _i, [_vp, _vp, _sz, _i, _vp]),
     ("nbx_leaf_plan_energy", _i, [_vp, _vp, _i, _d, _pd, _pd]),
     ("nbx_leaf_plan_get_potentials", _i, [_vp, _vp]),
@@ -217,6 +220,20 @@ class EvalInfo(ctypes.Structure):
     """nbx_eval_info of include/nbody_hip.h: what the one-shot evaluation ran."""
     _fields_ = [("kernel_ms", _c.c_float), ("refine_ms", _c.c_float), ("refine_tolerance", _d), ("refine_selected", _c.c_uint), ("refine_refined", _c.c_uint),
                 ("variant", _i), ("close_set_mode", _i)]
+
+
+class StepControl(ctypes.Structure):
+    """nbx_step_control of include/nbody_hip.h: how nbx_leaf_plan_step_kdk_adaptive chooses its steps."""
+    _fields_ = [("accel_length", _d), ("dt_min", _d), ("dt_max", _d), ("t_start", _d), ("t_end", _d), ("pow2", _i), ("reserved", _i)]
+
+
+class StepClock(ctypes.Structure):
+    """nbx_step_clock of include/nbody_hip.h: where an adaptive call left the device's clock."""
+    _fields_ = [("t", _d), ("dt_last", _d), ("a_max_last", _d), ("steps", _c.c_uint32), ("evaluations", _c.c_uint32), ("finished", _i), ("status", _i)]
+
+    def __repr__(self):
+        return (f"StepClock(t={self.t!r}, dt_last={self.dt_last!r}, a_max_last={self.a_max_last!r}, steps={self.steps}, "
+                f"evaluations={self.evaluations}, finished={self.finished}, status={self.status})")
 
 
 def set_default_refine(rel_tolerance: float, sigma_factor: float = 0.0):
@@ -443,6 +460,32 @@ class LeafPlan:
         v = ctypes.c_double(0.0)
         self._ck(self.lib.nbx_leaf_plan_max_accel(self.h, ctypes.byref(v)), "nbx_leaf_plan_max_accel")
         return v.value
+
+    def step_kdk_adaptive(self, ctx: "Context", law: int, G: float, accel_length: float, dt_min: float, dt_max: float, t_end: float = float("inf"),
+                          max_steps: int = 1 << 20, rebuild_every: int = 0, t_start: float = 0.0, pow2: bool = False) -> "StepClock":
+        """Kick-drift-kick with every step chosen on the device, dt = sqrt(accel_length / a_max) clamped to [dt_min, dt_max] (pow2:
+        dt_max / 2^j), until t_end or max_steps (nbx_leaf_plan_step_kdk_adaptive).  Returns the clock (which synchronises)."""
+        k = StepControl(float(accel_length), float(dt_min), float(dt_max), float(t_start), float(t_end), 1 if pow2 else 0, 0)
+        self._ck(self.lib.nbx_leaf_plan_step_kdk_adaptive(self.h, ctx.h, int(law), float(G), ctypes.byref(k), int(max_steps), int(rebuild_every)),
+                 "nbx_leaf_plan_step_kdk_adaptive")
+        return self.step_clock() if int(max_steps) > 0 else None
+
+    def step_clock(self) -> "StepClock":
+        """The device's clock as the last adaptive call left it (nbx_leaf_plan_get_step_clock); synchronises."""
+        k = StepClock()
+        self._ck(self.lib.nbx_leaf_plan_get_step_clock(self.h, ctypes.byref(k)), "nbx_leaf_plan_get_step_clock")
+        return k
+
+    def step_history(self):
+        """(a_max[k], dt[k]) of the evaluations the last adaptive call recorded, oldest first; the closing evaluation's dt is 0
+        (nbx_leaf_plan_get_step_history)."""
+        count = ctypes.c_size_t(0)
+        self._ck(self.lib.nbx_leaf_plan_get_step_history(self.h, None, None, 0, ctypes.byref(count)), "nbx_leaf_plan_get_step_history")
+        a, dt = np.zeros(count.value, dtype=np.float64), np.zeros(count.value, dtype=np.float64)
+        if count.value:
+            self._ck(self.lib.nbx_leaf_plan_get_step_history(self.h, a.ctypes.data, dt.ctypes.data, count.value, ctypes.byref(count)),
+                     "nbx_leaf_plan_get_step_history")
+        return a, dt
 
     def set_cells(self, cell_first_leaf, cell_leaf_count, far_offsets, far_cells):
         """The plan's far field (nbx_leaf_plan_set_cells): cells as leaf ranges and a CSR far list per target leaf; every evaluation

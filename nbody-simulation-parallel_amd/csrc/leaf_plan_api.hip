@@ -1,7 +1,8 @@
 // leaf_plan_api.hip -- the host side of the leaf-pair path behind the C ABI (include/nbody_hip.h): the one-shot call
 // nbx_leaf_pair_forces and the device-resident plan nbx_leaf_plan_*.  Validation, the choice of planner (leaf_plan.h on the host,
 // leaf_plan_device.h on the device), the octree built on the device (octree_device.h), and every entry point.  Every kick of
-// a plan is launch_kick_drift_slots (plan_kick, plan_enqueue_eval) and every stepping loop is plan_run_steps.  The kernels are
+// a plan is launch_kick_drift_slots (plan_kick, plan_enqueue_eval) and every fixed-step loop is plan_run_steps; the loop whose steps
+// are chosen on the device is plan_run_adaptive, with its kick read from the step clock.  The kernels are
 // leaf_pair_kernel.hip's (through leaf_near.h), leaf_far_kernel.hip's (leaf_far.h) and, for the potential, leaf_phi_kernel.hip's
 // (leaf_phi.h); device memory is device_block.h's.
 #include "../../include/nbody_hip.h"
@@ -128,6 +129,11 @@ struct nbx_leaf_plan {
     Block phi_raw;                  // staged Body<D> array of nbx_leaf_plan_potentials -- not `raw`: the masses of the last force evaluation may live there
     // ---- the largest acceleration (nbx_leaf_plan_max_accel): the reduction's 8-byte word, allocated when a caller first asks ----
     Block amax_block;
+    // ---- the step clock (nbx_leaf_plan_step_kdk_adaptive; nbx_internal.h: StepClock): allocated by the first adaptive call ----
+    Block clock_block;              // the clock and, kStepClockHistoryOffset behind it, the history of the last call
+    bool clock_valid = false;       // an adaptive call has gone through: the block holds its clock
+    int* stop_look = nullptr;       // pinned host word the loop's looks at the clock's `stopped` land in
+    hipEvent_t look_done = nullptr; // ... and the event behind the look in flight
 };
 
 namespace {
@@ -822,6 +828,9 @@ int nbx_leaf_plan_destroy(nbx_leaf_plan* p) {
     p->phi_block.release(all_idle);
     p->phi_raw.release(all_idle);
     p->amax_block.release(all_idle);
+    p->clock_block.release(all_idle);
+    if (p->stop_look) (void)hipHostFree(p->stop_look);
+    if (p->look_done) (void)hipEventDestroy(p->look_done);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     if (p->done) (void)hipEventDestroy(p->done);
@@ -1021,6 +1030,152 @@ int nbx_leaf_plan_step_octree(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, d
 int nbx_leaf_plan_step_octree_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, double dt, int nsteps, int rebuild_every) {
     if (int rc = check_octree_steps(p, c, law, nsteps, rebuild_every)) return rc;
     return plan_run_steps(p, c, law, G, dt, nsteps, rebuild_every, Scheme::KickDriftKick);
+}
+
+// ---- kick-drift-kick with the step chosen on the device (include/nbody_hip.h has the rule; state_kernels.hip the controller) ----
+static const char* step_control_fault(const nbx_step_control* k) {
+    if (!(k->accel_length > 0.0) || !std::isfinite(k->accel_length)) return "accel_length must be finite and > 0";
+    if (!(k->dt_min > 0.0) || !std::isfinite(k->dt_min)) return "dt_min must be finite and > 0";
+    if (!(k->dt_max >= k->dt_min) || !std::isfinite(k->dt_max)) return "dt_max must be finite and >= dt_min";
+    if (!std::isfinite(k->t_start)) return "t_start must be finite";
+    if (std::isnan(k->t_end) || (std::isinf(k->t_end) && k->t_end < 0.0)) return "t_end must be finite or +infinity";
+    if (k->pow2 != 0 && k->pow2 != 1) return "pow2 must be 0 or 1";
+    if (k->reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
+constexpr int kStopLookEvery = 16;   // evaluations between two looks at the clock's `stopped` (the context's close-set look's spacing)
+
+// The step clock's block with room for a call of max_steps steps, and what the loop's looks need.  Growing the block waits for
+// the plan's queued work first: an earlier call's kernels may still read the one held.
+static int plan_fit_clock(nbx_leaf_plan* p, hipStream_t s, int max_steps) {
+    const size_t need = kStepClockHistoryOffset + ((size_t)max_steps + 1) * 2 * sizeof(double);
+    if (p->clock_block.bytes() < need) {
+        if (p->clock_block) NBX_HIP_TRY(hipStreamSynchronize(s));
+        p->clock_valid = false;
+        NBX_HIP_TRY(nbx_block::allocate(p->clock_block, p->device, need));
+    }
+    if (!p->stop_look) NBX_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->stop_look), 64, hipHostMallocDefault));
+    if (!p->look_done) NBX_HIP_TRY(hipEventCreateWithFlags(&p->look_done, hipEventDisableTiming));
+    return NBX_OK;
+}
+
+// plan_run_steps' sibling: evaluations 0 .. max_steps, each followed by the reduction, the controller and the clock kick.  The host
+// knows neither the steps' sizes nor when the loop stops; what it queues behind the stop changes nothing (the positions stand, so
+// the sums come out the same; the controller records nothing and the kick is not applied).  It stops queueing once a look has
+// shown it the stop: before every rebuild after the first (the build reads back right behind it, so that wait costs nothing, and a
+// structure built behind the stop would not be the one the last kick was made on), and, without rebuilds, by a copy every
+// kStopLookEvery evaluations that is polled, never waited for.
+static int plan_run_adaptive(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, const nbx_step_control& k, int max_steps, int rebuild_every) {
+    if (max_steps == 0) return NBX_OK;
+    const bool rebuilds = rebuild_every > 0;
+    if (!rebuilds)
+        if (int src = plan_needs_structure(p)) return src;
+    if (int lrc = plan_check_law(p, law, c->mass_max)) return lrc;
+    hipStream_t s = c->stream;
+    PlanScope in(p, s);
+    if (in.rc) return in.rc;
+    if (int rc = plan_fit_clock(p, s, max_steps)) return rc;
+    StepClock* const clock = p->clock_block.as<StepClock>();
+    const double signedG = signed_G(law, G);
+    NBX_HIP_TRY(launch_step_clock_init(clock, k.accel_length, k.dt_min, k.dt_max, k.t_start, k.t_end, k.pow2, (uint32_t)max_steps + 1u, s));
+    p->clock_valid = true;
+    auto queued = [&]() {
+        plan_record_evaluation(p, law, signedG, c);
+        ctx_bodies_moved(c);
+        return plan_mark_done(p, s);
+    };
+    bool look_in_flight = false;
+    for (int e = 0; e <= max_steps; ++e) {
+        if (rebuilds) {
+            int rc = NBX_OK;
+            if (e % rebuild_every == 0) {
+                if (e > 0) {
+                    NBX_HIP_TRY(hipMemcpyAsync(p->stop_look, &clock->stopped, sizeof(int), hipMemcpyDeviceToHost, s));
+                    NBX_HIP_TRY(hipStreamSynchronize(s));
+                    if (*p->stop_look) break;
+                }
+                rc = plan_build_octree(p, c);
+            }
+            if (!rc) rc = plan_needs_structure(p);
+            if (rc) return rc;
+        } else if (e > 0 && e % kStopLookEvery == 0) {
+            if (look_in_flight && hipEventQuery(p->look_done) == hipSuccess) {
+                look_in_flight = false;
+                if (*p->stop_look) break;
+            }
+            (void)hipGetLastError();                        // hipErrorNotReady of the query is no failure
+            if (!look_in_flight) {
+                NBX_HIP_TRY(hipMemcpyAsync(p->stop_look, &clock->stopped, sizeof(int), hipMemcpyDeviceToHost, s));
+                NBX_HIP_TRY(hipEventRecord(p->look_done, s));
+                look_in_flight = true;
+            }
+        }
+        NBX_HIP_TRY(hipMemsetAsync(p->max_mass, 0, sizeof(uint32_t), s));
+        if (int rc = plan_gather_resident(p, c, s)) return rc;
+        if (int rc = plan_launch_pairs(p, law, s, false)) return rc;
+        NBX_HIP_TRY(launch_step_controller(p->sums, p->pslot_body, (uint32_t)p->pslots, p->dim, std::fabs(signedG), clock, e == max_steps, s));
+        NBX_HIP_TRY(launch_kick_drift_slots_clock(slot_kick_args(p, c, signedG, 0.0, 0.0, true), clock, s));
+        if (rebuilds)
+            if (int rc = queued()) return rc;
+    }
+    return queued();
+}
+
+int nbx_leaf_plan_step_kdk_adaptive(nbx_leaf_plan* p, nbx_ctx* c, int law, double G, const nbx_step_control* control, int max_steps,
+                                    int rebuild_every) {
+    // what needs no device first: the control, the law, the counts, then the two handles
+    if (!control) return fail(NBX_ERR_INVALID, "null argument");
+    if (const char* why = step_control_fault(control)) return fail(NBX_ERR_INVALID, why);
+    if (law < NBX_LAW_BRUTE || law > NBX_LAW_NEWTON) return fail(NBX_ERR_INVALID, "unknown law");
+    if (max_steps < 0 || max_steps > (1 << 20)) return fail(NBX_ERR_INVALID, "max_steps must be in [0, 1 << 20]");
+    if (rebuild_every < 0) return fail(NBX_ERR_INVALID, "rebuild_every must be >= 0");
+    if (!p || !c) return fail(NBX_ERR_INVALID, "null argument");
+    if (int rc = plan_check_ctx(p, c)) return rc;
+    if (rebuild_every > 0 && !p->octree) return fail(NBX_ERR_STATE, "the plan was not made by nbx_leaf_plan_create_octree");
+    return plan_run_adaptive(p, c, law, G, *control, max_steps, rebuild_every);
+}
+
+// the clock's record, read back on the plan's own stream behind the last queued work
+static int plan_read_clock(nbx_leaf_plan* p, StepClock* host) {
+    NBX_HIP_TRY(hipMemcpyAsync(host, p->clock_block.get(), sizeof(StepClock), hipMemcpyDeviceToHost, p->stream));
+    NBX_HIP_TRY(hipStreamSynchronize(p->stream));
+    return NBX_OK;
+}
+
+int nbx_leaf_plan_get_step_clock(nbx_leaf_plan* p, nbx_step_clock* out) {
+    if (!p || !out) return fail(NBX_ERR_INVALID, "null argument");
+    if (!p->clock_valid) return fail(NBX_ERR_STATE, "no adaptive call on this plan yet (nbx_leaf_plan_step_kdk_adaptive)");
+    PlanScope in(p, p->stream);
+    if (in.rc) return in.rc;
+    StepClock k;
+    if (int rc = plan_read_clock(p, &k)) return rc;
+    out->t = k.t; out->dt_last = k.prev; out->a_max_last = k.a_max_last;
+    out->steps = k.steps; out->evaluations = k.evaluations;
+    out->finished = k.finished; out->status = k.status;
+    return plan_mark_done(p, p->stream);
+}
+
+int nbx_leaf_plan_get_step_history(nbx_leaf_plan* p, double* a_max_out, double* dt_out, size_t capacity, size_t* count) {
+    if (!p || !count) return fail(NBX_ERR_INVALID, "null argument");
+    if (!p->clock_valid) return fail(NBX_ERR_STATE, "no adaptive call on this plan yet (nbx_leaf_plan_step_kdk_adaptive)");
+    PlanScope in(p, p->stream);
+    if (in.rc) return in.rc;
+    StepClock k;
+    if (int rc = plan_read_clock(p, &k)) return rc;
+    *count = k.recorded;
+    const size_t take = capacity < (size_t)k.recorded ? capacity : (size_t)k.recorded;
+    if (take && (a_max_out || dt_out)) {
+        std::vector<double> pairs;
+        try { pairs.resize(2 * take); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
+        NBX_HIP_TRY(hipMemcpyAsync(pairs.data(), p->clock_block.get() + kStepClockHistoryOffset, 2 * take * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        NBX_HIP_TRY(hipStreamSynchronize(p->stream));
+        for (size_t i = 0; i < take; ++i) {
+            if (a_max_out) a_max_out[i] = pairs[2 * i];
+            if (dt_out) dt_out[i] = pairs[2 * i + 1];
+        }
+    }
+    return plan_mark_done(p, p->stream);
 }
 
 // An observer like the potential calls: it reads the slot sums and the inverse map and writes its own 8-byte word.

@@ -275,6 +275,32 @@ hipError_t launch_kick_drift_slots(const SlotKickArgs& k, hipStream_t stream);
 hipError_t launch_slot_accel_max(const double* sums, const uint32_t* body_slot, uint32_t pslots, int dim, size_t n, double absG,
                                  unsigned long long* out, hipStream_t stream);
 
+// The device's step clock of nbx_leaf_plan_step_kdk_adaptive (include/nbody_hip.h has the rule): one block in device memory, this
+// record at its start and the history -- (a_max, dt) pairs, 16 bytes each -- kStepClockHistoryOffset bytes behind it.  The controller
+// (one thread behind every evaluation's reduction) writes it; the clock kick reads this evaluation's {dt_kick, dt_drift, drift,
+// apply}; the host reads `stopped` (a look it never waits for) and, when asked, the rest.
+struct StepClock {
+    unsigned long long amax_bits;      // the reduction's word (launch_step_controller zeroes it first)
+    double accel_length, dt_min, dt_max, t_end;
+    double t, prev, a_max_last;
+    double dt_kick, dt_drift;          // this evaluation's kick
+    int pow2, drift, apply;            // drift, apply: this evaluation's kick drifts / is made at all
+    int stopped, finished, status;
+    uint32_t steps, evaluations, recorded;
+    uint32_t capacity;                 // history entries the block has room for
+};
+constexpr size_t kStepClockHistoryOffset = 256;
+static_assert(sizeof(StepClock) <= kStepClockHistoryOffset, "the history starts behind the clock");
+// the clock as a call finds it: the control's values, t = t_start, nothing recorded
+hipError_t launch_step_clock_init(StepClock* clock, double accel_length, double dt_min, double dt_max, double t_start, double t_end, int pow2,
+                                  uint32_t capacity, hipStream_t stream);
+// launch_slot_accel_max's value into clock->amax_bits, reduced slot by slot (pslot_body[pslots]: the body of every slot, 0xffffffff for
+// a pad), and the controller behind it; `last`: this is evaluation number max_steps
+hipError_t launch_step_controller(const double* sums, const uint32_t* pslot_body, uint32_t pslots, int dim, double absG, StepClock* clock, bool last,
+                                  hipStream_t stream);
+// launch_kick_drift_slots with dt_kick, dt_drift and the two flags read from the clock (k's own are not read)
+hipError_t launch_kick_drift_slots_clock(const SlotKickArgs& k, const StepClock* clock, hipStream_t stream);
+
 // forces_out: AoS double[count][dim] on the device
 hipError_t launch_export_forces(const float* acc, int splits, int dim, unsigned pad, size_t count,
                                 double G, const double* m64, double* forces_out, hipStream_t stream);

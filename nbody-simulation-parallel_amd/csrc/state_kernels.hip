@@ -149,6 +149,114 @@ __global__ __launch_bounds__(256) void slot_accel_max_kernel(const double* __res
     if (threadIdx.x == 0 && s_max > *(volatile unsigned long long*)out) atomicMax(out, s_max);
 }
 
+// ---- the step chosen on the device (nbx_leaf_plan_step_kdk_adaptive; include/nbody_hip.h has the rule) ----
+// slot_accel_max_kernel's maximum taken slot by slot: a slot that holds a body (pslot_body is body_slot's inverse; a leaf's pad holds
+// 0xffffffff) contributes what that body contributes there, and a maximum does not depend on the order, so the word is the same bits.
+// One lane per slot reads its dim sums and its 4-byte body index coalesced (28 B per slot) where one lane per body gathers dim
+// scattered doubles -- the form for a reduction behind EVERY evaluation.
+__global__ __launch_bounds__(256) void slot_accel_max_by_slot_kernel(const double* __restrict__ sums, const uint32_t* __restrict__ pslot_body,
+                                                                     uint32_t pslots, int dim, double absG, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_max;
+    if (threadIdx.x == 0) s_max = 0ull;
+    __syncthreads();
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long ab = 0ull;
+    if (l < pslots && pslot_body[l] != 0xffffffffu) {
+        double s2 = 0.0;
+        for (int k = 0; k < dim; ++k) { const double s = sums[(size_t)k * pslots + l]; s2 += s * s; }
+        ab = (unsigned long long)__double_as_longlong(fabs(absG * sqrt(s2)));
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(ab, off);
+        ab = o > ab ? o : ab;
+    }
+    if ((threadIdx.x & 63u) == 0u && ab) atomicMax(&s_max, ab);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_max > *(volatile unsigned long long*)out) atomicMax(out, s_max);
+}
+
+__global__ void step_clock_init_kernel(StepClock* __restrict__ c, double accel_length, double dt_min, double dt_max, double t_start, double t_end,
+                                       int pow2, uint32_t capacity) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    c->amax_bits = 0ull;
+    c->accel_length = accel_length; c->dt_min = dt_min; c->dt_max = dt_max; c->t_end = t_end;
+    c->t = t_start; c->prev = 0.0; c->a_max_last = 0.0;
+    c->dt_kick = 0.0; c->dt_drift = 0.0;
+    c->pow2 = pow2; c->drift = 0; c->apply = 0;
+    c->stopped = 0; c->finished = 0; c->status = 0;
+    c->steps = 0u; c->evaluations = 0u; c->recorded = 0u;
+    c->capacity = capacity;
+}
+
+// The controller: one thread, behind slot_accel_max_kernel on the same stream (the stream orders them: no fence, no ticket), runs
+// the loop rule for the evaluation just reduced, in fp64 without contraction, and leaves this evaluation's kick in the clock.  Once
+// the loop has stopped every later evaluation finds apply = 0 and records nothing.
+__global__ void step_controller_kernel(StepClock* __restrict__ c, int last) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (c->stopped) { c->apply = 0; c->drift = 0; return; }
+    const double a_max = __longlong_as_double((long long)c->amax_bits);
+    double* const history = reinterpret_cast<double*>(reinterpret_cast<char*>(c) + kStepClockHistoryOffset);
+    c->evaluations += 1u;
+    c->a_max_last = a_max;
+    if (!(fabs(a_max) <= 1.7976931348623157e308)) {      // NaN or infinity: no kick with these sums
+        c->status = 1; c->stopped = 1; c->apply = 0; c->drift = 0;
+        return;
+    }
+    const double t = c->t, t_end = c->t_end, prev = c->prev;
+    const uint32_t slot = c->recorded;
+    if (t >= t_end || last) {                             // the closing half-kick
+        c->dt_kick = 0.5 * prev; c->dt_drift = 0.0;
+        c->drift = 0; c->apply = prev != 0.0 ? 1 : 0;
+        if (slot < c->capacity) { history[2 * (size_t)slot] = a_max; history[2 * (size_t)slot + 1] = 0.0; c->recorded = slot + 1u; }
+        c->finished = t >= t_end ? 1 : 0;
+        c->stopped = 1;
+        return;
+    }
+    const double raw = a_max == 0.0 ? __longlong_as_double(0x7ff0000000000000ll) : sqrt(c->accel_length / a_max);
+    const double dt_min = c->dt_min, dt_max = c->dt_max;
+    double dt;
+    if (c->pow2) {
+        dt = dt_max;
+        while (dt > raw && 0.5 * dt >= dt_min) dt = 0.5 * dt;
+    } else {
+        dt = raw < dt_min ? dt_min : raw;                 // min(max(raw, dt_min), dt_max)
+        dt = dt > dt_max ? dt_max : dt;
+    }
+    const double left = t_end - t;
+    if (dt >= left) { dt = left; c->t = t_end; }
+    else c->t = t + dt;
+    c->dt_kick = 0.5 * prev + 0.5 * dt; c->dt_drift = dt;
+    c->drift = dt != 0.0 ? 1 : 0; c->apply = 1;
+    c->prev = dt;
+    c->steps += 1u;
+    if (slot < c->capacity) { history[2 * (size_t)slot] = a_max; history[2 * (size_t)slot + 1] = dt; c->recorded = slot + 1u; }
+}
+
+// kick_drift_slots_kernel's body with the kick's and the drift's step and the two flags read from the clock (uniform addresses, the
+// same for every lane).  apply == 0: nothing is read or written.  drift == 0 is the pure kick: x64 and the fp32 chunk are neither
+// read nor written.
+__global__ __launch_bounds__(256) void kick_drift_slots_clock_kernel(SlotKickArgs a, const StepClock* __restrict__ clock) {
+    if (clock->apply == 0) return;
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= a.count) return;
+    const double dt_kick = clock->dt_kick, dt_drift = clock->dt_drift;
+    const bool drift = clock->drift != 0;
+    const int k = (int)blockIdx.y;
+    const double m = a.m64[l];
+    const uint32_t slot = a.body_slot[l];
+    const double sum = slot == 0xffffffffu ? 0.0 : a.sums[(size_t)k * a.pslots + slot];
+    const double F = (a.signedG * m) * sum;
+    double v = a.v64[(size_t)k * a.pad + l];
+    v += (F / m) * dt_kick;
+    a.v64[(size_t)k * a.pad + l] = v;
+    if (drift) {
+        double x = a.x64[(size_t)k * a.pad + l];
+        x += v * dt_drift;
+        a.x64[(size_t)k * a.pad + l] = x;
+        a.pos_chunk[(size_t)k * a.pad + l] = (float)x;
+    }
+}
+
 __global__ __launch_bounds__(256) void export_forces_kernel(const float* __restrict__ acc, int splits, int dim,
                                                             unsigned pad, size_t count, double G,
                                                             const double* __restrict__ m64,
@@ -273,6 +381,30 @@ hipError_t launch_slot_accel_max(const double* sums, const uint32_t* body_slot, 
     hipError_t e = hipMemsetAsync(out, 0, sizeof(unsigned long long), stream);
     if (e != hipSuccess || n == 0) return e;
     hipLaunchKernelGGL(slot_accel_max_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, sums, body_slot, pslots, dim, n, absG, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_step_clock_init(StepClock* clock, double accel_length, double dt_min, double dt_max, double t_start, double t_end, int pow2,
+                                  uint32_t capacity, hipStream_t stream) {
+    hipLaunchKernelGGL(step_clock_init_kernel, dim3(1), dim3(64), 0, stream, clock, accel_length, dt_min, dt_max, t_start, t_end, pow2, capacity);
+    return hipGetLastError();
+}
+
+hipError_t launch_step_controller(const double* sums, const uint32_t* pslot_body, uint32_t pslots, int dim, double absG, StepClock* clock, bool last,
+                                  hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(&clock->amax_bits, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
+    if (pslots) {
+        hipLaunchKernelGGL(slot_accel_max_by_slot_kernel, dim3(blocks_for(pslots)), dim3(256), 0, stream, sums, pslot_body, pslots, dim, absG, &clock->amax_bits);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(step_controller_kernel, dim3(1), dim3(64), 0, stream, clock, last ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_kick_drift_slots_clock(const SlotKickArgs& k, const StepClock* clock, hipStream_t stream) {
+    if (k.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(kick_drift_slots_clock_kernel, dim3(blocks_for(k.count), (unsigned)k.dim, 1), dim3(256), 0, stream, k, clock);
     return hipGetLastError();
 }
 

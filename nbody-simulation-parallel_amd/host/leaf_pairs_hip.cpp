@@ -104,6 +104,15 @@ void LeafPairSimulationHip<D>::step_kdk(LeafLaw law, double G, double dt, int ns
     if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::step_kdk", rc);
 }
 template <int D>
+nbx_step_clock LeafPairSimulationHip<D>::step_kdk_adaptive(LeafLaw law, double G, const nbx_step_control& control, int max_steps) {
+    nbx_step_clock clock{};
+    clock.t = control.t_start;
+    int rc = nbx_leaf_plan_step_kdk_adaptive(plan_, ctx_, static_cast<int>(law), G, &control, max_steps, 0);
+    if (!rc && max_steps > 0) rc = nbx_leaf_plan_get_step_clock(plan_, &clock);
+    if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::step_kdk_adaptive", rc);
+    return clock;
+}
+template <int D>
 void LeafPairSimulationHip<D>::synchronize() {
     const int rc = nbx_ctx_synchronize(ctx_);
     if (rc != NBX_OK) raise_leaf("LeafPairSimulationHip::synchronize", rc);
@@ -194,22 +203,53 @@ void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth,
 }
 
 namespace {
-// the reference law's step loop under either integrator, the bodies brought back at the end
+// the smallest and largest step of the plan's last adaptive call, from its history (the closing evaluation's entry has dt = 0)
+int adaptive_step_range(nbx_leaf_plan* plan, double* dt_smallest, double* dt_largest) {
+    *dt_smallest = *dt_largest = 0.0;
+    std::size_t count = 0;
+    int rc = nbx_leaf_plan_get_step_history(plan, nullptr, nullptr, 0, &count);
+    if (rc || !count) return rc;
+    std::vector<double> dt(count);
+    rc = nbx_leaf_plan_get_step_history(plan, nullptr, dt.data(), count, &count);
+    for (std::size_t i = 0; !rc && i < count; ++i) {
+        if (dt[i] == 0.0) continue;
+        *dt_smallest = *dt_smallest == 0.0 ? dt[i] : std::min(*dt_smallest, dt[i]);
+        *dt_largest = std::max(*dt_largest, dt[i]);
+    }
+    return rc;
+}
+
+// one adaptive call and what it reports; max_steps == 0 does nothing and reports a clock standing at t_start
+int adaptive_steps(nbx_leaf_plan* plan, nbx_ctx* ctx, int law, double G, int max_steps, int rebuild_every, TreeAdaptiveSteps* steps, const char* where) {
+    if (!steps) throw std::runtime_error(std::string(where) + ": TreeIntegrator::KickDriftKickAdaptive needs its TreeAdaptiveSteps");
+    steps->clock = nbx_step_clock{};
+    steps->clock.t = steps->control.t_start;
+    steps->dt_smallest = steps->dt_largest = 0.0;
+    int rc = nbx_leaf_plan_step_kdk_adaptive(plan, ctx, law, G, &steps->control, max_steps, rebuild_every);
+    if (!rc && max_steps > 0) rc = nbx_leaf_plan_get_step_clock(plan, &steps->clock);
+    if (!rc && max_steps > 0) rc = adaptive_step_range(plan, &steps->dt_smallest, &steps->dt_largest);
+    return rc;
+}
+
+// the reference law's step loop under any integrator, the bodies brought back at the end
 template <int D>
-void tree_leaf_steps(OctreeOnDevice<D>& tree, std::vector<Body<D>>& bodies, double dt, int nsteps, int rebuild_every, TreeIntegrator integrator, const char* where) {
+void tree_leaf_steps(OctreeOnDevice<D>& tree, std::vector<Body<D>>& bodies, double dt, int nsteps, int rebuild_every, TreeIntegrator integrator, TreeAdaptiveSteps* steps,
+                     const char* where) {
     const int law = static_cast<int>(LeafLaw::TreeLeaf);
-    int rc = integrator == TreeIntegrator::KickDriftKick ? nbx_leaf_plan_step_octree_kdk(tree.plan, tree.ctx, law, NBX_REFERENCE_G, dt, nsteps, rebuild_every)
-                                                         : nbx_leaf_plan_step_octree(tree.plan, tree.ctx, law, NBX_REFERENCE_G, dt, nsteps, rebuild_every);
+    int rc = integrator == TreeIntegrator::KickDriftKickAdaptive ? adaptive_steps(tree.plan, tree.ctx, law, NBX_REFERENCE_G, nsteps, rebuild_every, steps, where)
+             : integrator == TreeIntegrator::KickDriftKick       ? nbx_leaf_plan_step_octree_kdk(tree.plan, tree.ctx, law, NBX_REFERENCE_G, dt, nsteps, rebuild_every)
+                                                                 : nbx_leaf_plan_step_octree(tree.plan, tree.ctx, law, NBX_REFERENCE_G, dt, nsteps, rebuild_every);
     if (!rc) rc = nbx_ctx_download_bodies(tree.ctx, bodies.data(), sizeof(Body<D>));
     if (rc != NBX_OK) raise_leaf(where, rc);
 }
 }  // namespace
 
 template <int D>
-void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, TreeIntegrator integrator) {
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, TreeIntegrator integrator,
+                          TreeAdaptiveSteps* steps) {
     if (bodies.empty()) return;
     OctreeOnDevice<D> tree(bodies, theta, depth, "barnes_hut_hip_steps", -1, far_order);
-    tree_leaf_steps<D>(tree, bodies, dt, nsteps, rebuild_every, integrator, "barnes_hut_hip_steps");
+    tree_leaf_steps<D>(tree, bodies, dt, nsteps, rebuild_every, integrator, steps, "barnes_hut_hip_steps");
 }
 
 namespace {
@@ -241,11 +281,11 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
 
 template <int D>
 void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every, int far_order,
-                                   TreeIntegrator integrator) {
+                                   TreeIntegrator integrator, TreeAdaptiveSteps* steps) {
     check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_steps");
     if (bodies.empty()) return;
     OctreeOnDevice<D> tree(bodies, theta, max_depth, "barnes_hut_hip_adaptive_steps", leaf_capacity, far_order);
-    tree_leaf_steps<D>(tree, bodies, dt, nsteps, rebuild_every, integrator, "barnes_hut_hip_adaptive_steps");
+    tree_leaf_steps<D>(tree, bodies, dt, nsteps, rebuild_every, integrator, steps, "barnes_hut_hip_adaptive_steps");
 }
 
 template <int D>
@@ -315,6 +355,20 @@ template <int D>
 void BarnesHutNewtonHip<D>::step_kdk(double dt, int nsteps, int rebuild_every) {
     const int rc = nbx_leaf_plan_step_octree_kdk(plan_, ctx_, NBX_LAW_NEWTON, G_, dt, nsteps, rebuild_every);
     if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::step_kdk", rc);
+}
+template <int D>
+nbx_step_clock BarnesHutNewtonHip<D>::step_kdk_adaptive(const nbx_step_control& control, int max_steps, int rebuild_every) {
+    nbx_step_clock clock{};
+    clock.t = control.t_start;
+    int rc = nbx_leaf_plan_step_kdk_adaptive(plan_, ctx_, NBX_LAW_NEWTON, G_, &control, max_steps, rebuild_every);
+    if (!rc && max_steps > 0) rc = nbx_leaf_plan_get_step_clock(plan_, &clock);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::step_kdk_adaptive", rc);
+    return clock;
+}
+template <int D>
+void BarnesHutNewtonHip<D>::step_range(double* dt_smallest, double* dt_largest) {
+    const int rc = adaptive_step_range(plan_, dt_smallest, dt_largest);
+    if (rc != NBX_OK) raise_leaf("BarnesHutNewtonHip::step_range", rc);
 }
 template <int D>
 double BarnesHutNewtonHip<D>::max_accel() {
@@ -388,31 +442,48 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
     sim.step(dt, nsteps, rebuild_every);
     sim.download(bodies);
 }
+namespace {
+// the Newtonian object's step loop under any integrator
+template <int D>
+void newton_steps(BarnesHutNewtonHip<D>& sim, double dt, int nsteps, int rebuild_every, TreeIntegrator integrator, TreeAdaptiveSteps* steps, const char* where) {
+    if (integrator == TreeIntegrator::KickDriftKickAdaptive) {
+        if (!steps) throw std::runtime_error(std::string(where) + ": TreeIntegrator::KickDriftKickAdaptive needs its TreeAdaptiveSteps");
+        steps->clock = sim.step_kdk_adaptive(steps->control, nsteps, rebuild_every);
+        steps->dt_smallest = steps->dt_largest = 0.0;
+        if (nsteps > 0) sim.step_range(&steps->dt_smallest, &steps->dt_largest);
+    } else if (integrator == TreeIntegrator::KickDriftKick) {
+        sim.step_kdk(dt, nsteps, rebuild_every);
+    } else {
+        sim.step(dt, nsteps, rebuild_every);
+    }
+}
+}  // namespace
+
 template <int D>
 void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, double G, double epsilon,
-                          TreeIntegrator integrator) {
+                          TreeIntegrator integrator, TreeAdaptiveSteps* steps) {
     if (bodies.empty()) return;
     BarnesHutNewtonHip<D> sim(bodies, theta, -1, depth, far_order, G, epsilon);
-    if (integrator == TreeIntegrator::KickDriftKick) sim.step_kdk(dt, nsteps, rebuild_every); else sim.step(dt, nsteps, rebuild_every);
+    newton_steps<D>(sim, dt, nsteps, rebuild_every, integrator, steps, "barnes_hut_hip_steps");
     sim.download(bodies);
 }
 template <int D>
 void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every,
-                                   int far_order, double G, double epsilon, TreeIntegrator integrator) {
+                                   int far_order, double G, double epsilon, TreeIntegrator integrator, TreeAdaptiveSteps* steps) {
     check_capacity(leaf_capacity, "barnes_hut_hip_adaptive_steps");
     if (bodies.empty()) return;
     BarnesHutNewtonHip<D> sim(bodies, theta, leaf_capacity, max_depth, far_order, G, epsilon);
-    if (integrator == TreeIntegrator::KickDriftKick) sim.step_kdk(dt, nsteps, rebuild_every); else sim.step(dt, nsteps, rebuild_every);
+    newton_steps<D>(sim, dt, nsteps, rebuild_every, integrator, steps, "barnes_hut_hip_adaptive_steps");
     sim.download(bodies);
 }
-template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, TreeIntegrator);
-template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int, TreeIntegrator);
-template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int, TreeIntegrator);
-template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int, TreeIntegrator);
-template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, double, double, TreeIntegrator);
-template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int, double, double, TreeIntegrator);
-template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int, double, double, TreeIntegrator);
-template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int, double, double, TreeIntegrator);
+template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, TreeIntegrator, TreeAdaptiveSteps*);
+template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int, TreeIntegrator, TreeAdaptiveSteps*);
+template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int, TreeIntegrator, TreeAdaptiveSteps*);
+template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int, TreeIntegrator, TreeAdaptiveSteps*);
+template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, double, double, TreeIntegrator, TreeAdaptiveSteps*);
+template void barnes_hut_hip_steps<3>(std::vector<Body<3>>&, double, int, double, int, int, int, double, double, TreeIntegrator, TreeAdaptiveSteps*);
+template void barnes_hut_hip_adaptive_steps<2>(std::vector<Body<2>>&, double, int, int, double, int, int, int, double, double, TreeIntegrator, TreeAdaptiveSteps*);
+template void barnes_hut_hip_adaptive_steps<3>(std::vector<Body<3>>&, double, int, int, double, int, int, int, double, double, TreeIntegrator, TreeAdaptiveSteps*);
 template std::vector<Vector<2>> barnes_hut_hip_n_body<2>(const std::vector<Body<2>>&, double, int, int, double, double);
 template std::vector<Vector<3>> barnes_hut_hip_n_body<3>(const std::vector<Body<3>>&, double, int, int, double, double);
 template void barnes_hut_hip_steps<2>(std::vector<Body<2>>&, double, int, double, int, int, int, double, double);

@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "nbody_hip.h"   // nbx_step_control, nbx_step_clock: what the adaptive step loops take and return
+
 #if __has_include("nbody_types.h")
 #include "nbody_types.h"
 #else
@@ -59,6 +61,9 @@ public:
     // nsteps kick-drift-kick steps (nbx_leaf_plan_step_kdk; extension, second order): nsteps + 1 evaluations, positions and velocities at
     // one time afterwards, asynchronous
     void step_kdk(LeafLaw law, double G, double dt, int nsteps);
+    // kick-drift-kick with every step chosen on the device from the evaluation just made (nbx_leaf_plan_step_kdk_adaptive): up to
+    // max_steps steps towards control.t_end; returns the device's clock (which synchronises)
+    nbx_step_clock step_kdk_adaptive(LeafLaw law, double G, const nbx_step_control& control, int max_steps);
     void synchronize();   // waits for the steps queued so far
     void download(std::vector<Body<D>>& bodies);
     // 0 (NBX_FAR_MONOPOLE, every object's start) or 1 (NBX_FAR_QUADRUPOLE): the far cells' second-order term (nbx_leaf_plan_set_far_order)
@@ -124,12 +129,22 @@ void barnes_hut_hip_adaptive_leaves(const std::vector<Body<D>>& bodies, double t
 // The integrator of the step loops below.  KickDrift is the reference helpers' order and what every signature without an integrator
 // means; KickDriftKick is the synchronised second-order leapfrog (nbx_leaf_plan_step_octree_kdk: nsteps + 1 evaluations, the tree
 // built again before evaluation e when e % rebuild_every == 0, positions and velocities at one time afterwards).
-enum class TreeIntegrator { KickDrift, KickDriftKick };
+// KickDriftKickAdaptive is that loop with every step chosen on the device (nbx_leaf_plan_step_kdk_adaptive): it needs `steps`, whose
+// control says how; dt is not read (control.dt_max bounds the steps) and nsteps is the cap on their number.
+enum class TreeIntegrator { KickDrift, KickDriftKick, KickDriftKickAdaptive };
+// What KickDriftKickAdaptive takes (control) and gives back: the device's clock and the smallest and largest step it took
+// (both 0 when it took none).
+struct TreeAdaptiveSteps {
+    nbx_step_control control{};
+    nbx_step_clock clock{};
+    double dt_smallest = 0.0, dt_largest = 0.0;
+};
 template <int D>
-void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, TreeIntegrator integrator);
+void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, TreeIntegrator integrator,
+                          TreeAdaptiveSteps* steps = nullptr);
 template <int D>
 void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every, int far_order,
-                                   TreeIntegrator integrator);
+                                   TreeIntegrator integrator, TreeAdaptiveSteps* steps = nullptr);
 
 // ---- softened Newtonian gravity through the tree (extension; NBX_LAW_NEWTON) ----
 // The four calls above under F_i = +G m_i sum_j m_j d / (r^2 + epsilon^2)^(3/2): the same trees, lists and far orders, with the
@@ -146,10 +161,10 @@ void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, i
                                    int far_order, double G, double epsilon);
 template <int D>
 void barnes_hut_hip_steps(std::vector<Body<D>>& bodies, double theta, int depth, double dt, int nsteps, int rebuild_every, int far_order, double G, double epsilon,
-                          TreeIntegrator integrator);
+                          TreeIntegrator integrator, TreeAdaptiveSteps* steps = nullptr);
 template <int D>
 void barnes_hut_hip_adaptive_steps(std::vector<Body<D>>& bodies, double theta, int leaf_capacity, int max_depth, double dt, int nsteps, int rebuild_every,
-                                   int far_order, double G, double epsilon, TreeIntegrator integrator);
+                                   int far_order, double G, double epsilon, TreeIntegrator integrator, TreeAdaptiveSteps* steps = nullptr);
 
 // The same system kept on the device between chunks of steps: a context with the bodies and a plan with the octree built from them
 // (leaf_capacity < 0: fixed depth, depth 0 = barnes_hut_hip_depth; otherwise the adaptive tree down to `depth`).  energy() is the
@@ -167,6 +182,10 @@ public:
     std::vector<Vector<D>> forces();                          // of the bodies as they stand, on the tree as it stands
     void step(double dt, int nsteps, int rebuild_every = 1);  // nbx_leaf_plan_step_octree
     void step_kdk(double dt, int nsteps, int rebuild_every = 1);   // nbx_leaf_plan_step_octree_kdk: kick-drift-kick, x and v at one time afterwards
+    // nbx_leaf_plan_step_kdk_adaptive: up to max_steps steps towards control.t_end, each chosen on the device; returns the clock
+    // (which synchronises).  A caller who chains calls passes the last clock's t as control.t_start.
+    nbx_step_clock step_kdk_adaptive(const nbx_step_control& control, int max_steps, int rebuild_every = 1);
+    void step_range(double* dt_smallest, double* dt_largest);  // over the steps of the last adaptive call (nbx_leaf_plan_get_step_history); 0, 0 if none
     double max_accel();                                       // largest |F_i| / m_i of the last evaluation (nbx_leaf_plan_max_accel); synchronises
     void energy(double* kinetic, double* potential);          // synchronises
     void tree_energy(double* kinetic, double* potential);     // synchronises

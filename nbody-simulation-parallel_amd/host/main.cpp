@@ -18,6 +18,7 @@
 #include <functional>
 #include <iomanip>
 #include <iostream>
+#include <limits>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -47,7 +48,11 @@ struct Options {
     double G = ::G;                 // --G: coupling constant of the HIP stepping loop (default: the reference's)
     int energy_every = 0;           // --energy-every k: log E and |dE/E0| every k steps of the loop
     bool energy_tree = false;       // --energy-tree: behind each energy line of the tree's Newtonian step loop, the same line from the tree itself
-    std::string integrator = "kd";  // --integrator kd|kdk: kick-drift as the reference helpers are ordered, or kick-drift-kick (extension)
+    std::string integrator = "kd";  // --integrator kd|kdk|kdka: kick-drift as the reference helpers are ordered, kick-drift-kick (extension), or (-m t) that with the steps chosen on the device
+    double accel_length = 0.0;      // --accel-length c: kdka's dt = sqrt(c / a_max), clamped to [--dt-min, --dt]
+    double dt_min = 0.0;            // --dt-min: kdka's smallest step (default: --dt / 1024)
+    double t_end = std::numeric_limits<double>::infinity();   // --t-end: kdka stops there (default: after --steps steps)
+    bool pow2 = false;              // --pow2: kdka's steps are --dt / 2^j
     std::string law = "reference";  // --law reference|newton: pair law of the stepping loop (newton: extension, needs --softening)
     double softening = 0.0;         // --softening eps: Plummer-softened law in the stepping loop (extension; 0 = reference law)
     std::vector<int> devices;       // --gpus / --devices: shard the HIP rows over these GPUs (one process)
@@ -296,10 +301,24 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
     };
     // --integrator kdk: every `-m t` step loop below runs kick-drift-kick (nbx_leaf_plan_step_octree_kdk) and its rows carry `_kdk`;
     // without it the loops, their names and their lines are kick-drift's alone
-    const bool tree_kdk = opt.integrator == "kdk";
-    const std::string kdk = tree_kdk ? "_kdk" : "";
-    const std::string kdk_words = tree_kdk ? " (kick-drift-kick)" : "";
-    const TreeIntegrator tree_integrator = tree_kdk ? TreeIntegrator::KickDriftKick : TreeIntegrator::KickDrift;
+    // --integrator kdka: kick-drift-kick with every step chosen on the device (nbx_leaf_plan_step_kdk_adaptive): --dt is the largest
+    // step and --steps the cap, the rows carry `_kdka`, and a line behind each gives the steps taken, t reached and the range of dt
+    const bool tree_kdk = opt.integrator == "kdk", tree_kdka = opt.integrator == "kdka";
+    const std::string kdk = tree_kdk ? "_kdk" : tree_kdka ? "_kdka" : "";
+    const std::string kdk_words = tree_kdk ? " (kick-drift-kick)" : tree_kdka ? " at most (kick-drift-kick, steps chosen on the device)" : "";
+    const TreeIntegrator tree_integrator = tree_kdk ? TreeIntegrator::KickDriftKick : tree_kdka ? TreeIntegrator::KickDriftKickAdaptive : TreeIntegrator::KickDrift;
+    TreeAdaptiveSteps chosen;
+    chosen.control.accel_length = opt.accel_length;
+    chosen.control.dt_min = opt.dt_min > 0.0 ? opt.dt_min : opt.dt / 1024.0;
+    chosen.control.dt_max = opt.dt;
+    chosen.control.t_start = 0.0;
+    chosen.control.t_end = opt.t_end;
+    chosen.control.pow2 = opt.pow2 ? 1 : 0;
+    TreeAdaptiveSteps* const adaptive_steps = tree_kdka ? &chosen : nullptr;
+    auto adaptive_line = [&](unsigned steps, double t, double dt_smallest, double dt_largest, bool finished) {
+        out << "Adaptive steps: " << steps << " taken, t = " << std::setprecision(12) << t << ", dt " << dt_smallest << " .. " << dt_largest << std::setprecision(6)
+            << (finished ? ", t_end reached" : "") << std::endl;
+    };
     for (int order = 0; order <= opt.far_order && m.find('t') != std::string::npos; ++order) {
         const std::string quad = order ? "_quad" : "";
         if (opt.leaf_cap > 0) {
@@ -327,7 +346,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                 if (opt.steps > 0) {
                     std::vector<Body<D>> state = bodies;
                     const long long step_us = safely_execute(log, "BarnesHut_HIP_adaptive_steps" + quad + kdk, [&] {
-                        barnes_hut_hip_adaptive_steps<D>(state, opt.theta, opt.leaf_cap, max_depth, opt.dt, opt.steps, 1, order, tree_integrator);
+                        barnes_hut_hip_adaptive_steps<D>(state, opt.theta, opt.leaf_cap, max_depth, opt.dt, opt.steps, 1, order, tree_integrator, adaptive_steps);
                         return 0;
                     });
                     if (step_us >= 0) {
@@ -336,6 +355,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                         csv << std::endl;
                         out << "Barnes-Hut on HIP (adaptive), " << opt.steps << " steps of dt " << opt.dt << kdk_words << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
                             << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
+                        if (tree_kdka) adaptive_line(chosen.clock.steps, chosen.clock.t, chosen.dt_smallest, chosen.dt_largest, chosen.clock.finished != 0);
                         if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP_adaptive_steps" + quad + kdk + ".f64", state);
                     }
                 }
@@ -360,8 +380,8 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                 if (!opt.dump.empty()) dump_raw(opt.dump + "_BarnesHut_HIP" + quad + ".f64", forces);
                 if (opt.steps > 0) {
                     std::vector<Body<D>> state = bodies;
-                    const long long step_us = safely_execute(log, "BarnesHut_HIP_steps" + quad + kdk, [&] { barnes_hut_hip_steps<D>(state, opt.theta, depth, opt.dt, opt.steps, 1, order, tree_integrator); return 0; });
-                    if (step_us >= 0 && tree_kdk) {   // the kick-drift loop of this tree has never had a CSV row: its output stays as it is
+                    const long long step_us = safely_execute(log, "BarnesHut_HIP_steps" + quad + kdk, [&] { barnes_hut_hip_steps<D>(state, opt.theta, depth, opt.dt, opt.steps, 1, order, tree_integrator, adaptive_steps); return 0; });
+                    if (step_us >= 0 && (tree_kdk || tree_kdka)) {   // the kick-drift loop of this tree has never had a CSV row: its output stays as it is
                         csv << "BarnesHut_HIP_steps" << quad << kdk << "," << n << "," << D;
                         write_time(csv, static_cast<double>(step_us) / 1e6);
                         csv << std::endl;
@@ -369,6 +389,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                     if (step_us >= 0)
                         out << "Barnes-Hut on HIP, " << opt.steps << " steps of dt " << opt.dt << kdk_words << " rebuilding the tree every step: " << static_cast<double>(step_us) / 1e6
                             << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps << " ms per step, upload and download included)" << std::endl;
+                    if (step_us >= 0 && tree_kdka) adaptive_line(chosen.clock.steps, chosen.clock.t, chosen.dt_smallest, chosen.dt_largest, chosen.clock.finished != 0);
                 }
             }
             out << std::endl;
@@ -431,6 +452,8 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                 if (!opt.dump.empty()) dump_raw(opt.dump + "_" + name + ".f64", forces);
                 if (opt.steps > 0) {
                     std::vector<Body<D>> state = bodies;
+                    nbx_step_clock newton_clock{};
+                    double newton_dt_smallest = 0.0, newton_dt_largest = 0.0;
                     const long long step_us = safely_execute(log, name + "_steps" + kdk, [&] {
                         BarnesHutNewtonHip<D> sim(bodies, opt.theta, capacity, depth, order, opt.G, opt.softening);
                         double ke = 0.0, pe = 0.0, e0 = 0.0, e0_tree = 0.0;
@@ -454,16 +477,36 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                             out << "step 0  E = " << std::setprecision(12) << e0 << "  (kinetic " << ke << ", potential " << pe << ")" << std::endl;
                             if (opt.energy_tree) tree_line(0);
                         }
+                        newton_clock = nbx_step_clock{};
+                        newton_dt_smallest = newton_dt_largest = 0.0;
+                        unsigned taken = 0;
                         for (int done = 0; done < opt.steps;) {
                             const int k = std::min(chunk, opt.steps - done);
-                            if (tree_kdk) sim.step_kdk(opt.dt, k, 1); else sim.step(opt.dt, k, 1);   // kdk: x and v at one time, the energies synchronised
-                            done += k;
+                            if (tree_kdka) {   // chained calls of k steps: each ends synchronised, the next starts at its t
+                                nbx_step_control control = chosen.control;
+                                control.t_start = taken ? newton_clock.t : control.t_start;
+                                newton_clock = sim.step_kdk_adaptive(control, k, 1);
+                                double lo = 0.0, hi = 0.0;
+                                sim.step_range(&lo, &hi);
+                                if (lo > 0.0) newton_dt_smallest = newton_dt_smallest > 0.0 ? std::min(newton_dt_smallest, lo) : lo;
+                                newton_dt_largest = std::max(newton_dt_largest, hi);
+                                taken += newton_clock.steps;
+                                done += static_cast<int>(newton_clock.steps);
+                                if (newton_clock.finished || newton_clock.status || newton_clock.steps == 0) done = opt.steps;   // the last energy line, then out
+                            } else {
+                                if (tree_kdk) sim.step_kdk(opt.dt, k, 1); else sim.step(opt.dt, k, 1);   // kdk: x and v at one time, the energies synchronised
+                                done += k;
+                                taken += static_cast<unsigned>(k);
+                            }
+                            newton_clock.steps = taken;
                             if (opt.energy_every > 0) {
                                 sim.energy(&ke, &pe);
-                                out << "step " << done << "  E = " << std::setprecision(12) << ke + pe << "  |dE/E0| = " << std::setprecision(3)
+                                out << "step " << taken << "  E = " << std::setprecision(12) << ke + pe << "  |dE/E0| = " << std::setprecision(3)
                                     << std::abs((ke + pe - e0) / e0) << std::setprecision(6) << "  (kinetic " << ke << ", potential " << pe
-                                    << ", 2K/|U| " << 2.0 * ke / std::abs(pe) << ")" << std::endl;
-                                if (opt.energy_tree) tree_line(done);
+                                    << ", 2K/|U| " << 2.0 * ke / std::abs(pe) << ")";
+                                if (tree_kdka) out << "  t = " << std::setprecision(12) << newton_clock.t << std::setprecision(6);
+                                out << std::endl;
+                                if (opt.energy_tree) tree_line(static_cast<int>(taken));
                             }
                         }
                         sim.download(state);
@@ -477,6 +520,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                         out << "Barnes-Hut on HIP (Newtonian law), " << opt.steps << " steps of dt " << opt.dt << kdk_words << " rebuilding the tree every step: "
                             << static_cast<double>(step_us) / 1e6 << " s (" << static_cast<double>(step_us) / 1e3 / opt.steps
                             << " ms per step, upload, download and energies included)" << std::endl;
+                        if (tree_kdka) adaptive_line(newton_clock.steps, newton_clock.t, newton_dt_smallest, newton_dt_largest, newton_clock.finished != 0);
                         if (!opt.dump.empty()) dump_raw(opt.dump + "_" + name + "_steps" + kdk + ".f64", state);
                     }
                 }
@@ -651,6 +695,10 @@ void usage(const char* argv0) {
               << "      --integrator <kd|kdk> kd = update_body_velocities then update_body_positions per step (default, first order);" << std::endl
               << "                      kdk = the same helpers as a synchronised kick-drift-kick leapfrog (extension, second order)" << std::endl
               << "                      with -m t: the tree's step loops run kick-drift-kick too and their rows carry _kdk" << std::endl
+              << "                      kdka (-m t alone) = kick-drift-kick with every step chosen on the device, dt = sqrt(c / a_max) from the largest" << std::endl
+              << "                      acceleration of the evaluation just made; --dt is the largest step, --steps the cap, rows carry _kdka" << std::endl
+              << "      --accel-length <c> kdka's c (a length: eta^2 x softening is the usual choice); --dt-min <t> its smallest step (default --dt / 1024);" << std::endl
+              << "                      --t-end <t> where it stops (default: after --steps steps); --pow2: its steps are --dt / 2^j" << std::endl
               << "      --law <reference|newton> Pair law of the stepping loop: the reference's r^-4 form (default) or the attractive" << std::endl
               << "                      softened Newtonian law (extension; needs --softening; Plummer velocities then use --G)" << std::endl
               << "                      with -m t: BarnesHut_HIP_newton rows behind the reference-law rows, judged against the all-pairs forces" << std::endl
@@ -731,10 +779,18 @@ int main(int argc, char* argv[]) {
             opt.softening = std::stod(argv[++i]);
         } else if (arg == "--integrator" && has_value) {
             opt.integrator = argv[++i];
-            if (opt.integrator != "kd" && opt.integrator != "kdk") {
-                std::cerr << "Error: --integrator must be kd or kdk" << std::endl;
+            if (opt.integrator != "kd" && opt.integrator != "kdk" && opt.integrator != "kdka") {
+                std::cerr << "Error: --integrator must be kd, kdk or kdka" << std::endl;
                 return 1;
             }
+        } else if (arg == "--accel-length" && has_value) {
+            opt.accel_length = std::stod(argv[++i]);
+        } else if (arg == "--dt-min" && has_value) {
+            opt.dt_min = std::stod(argv[++i]);
+        } else if (arg == "--t-end" && has_value) {
+            opt.t_end = std::stod(argv[++i]);
+        } else if (arg == "--pow2") {
+            opt.pow2 = true;
         } else if (arg == "--law" && has_value) {
             opt.law = argv[++i];
             if (opt.law != "reference" && opt.law != "newton") {
@@ -789,6 +845,16 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    if (opt.integrator == "kdka") {
+        if (opt.methods.empty() || opt.methods.find_first_of("ag") != std::string::npos) {
+            std::cerr << "Error: --integrator kdka is the tree's step loop: use it with -m t" << std::endl;
+            return 1;
+        }
+        if (!(opt.accel_length > 0.0)) {
+            std::cerr << "Error: --integrator kdka needs --accel-length c > 0 (dt = sqrt(c / a_max))" << std::endl;
+            return 1;
+        }
+    }
     set_hip_devices(opt.devices);
     if (opt.refine >= 0.0) set_hip_refine(opt.refine);
     if (opt.methods.empty() || opt.methods.find_first_of("agpt") != std::string::npos)

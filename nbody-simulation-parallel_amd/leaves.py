@@ -620,3 +620,78 @@ def leapfrog_spec(bodies: np.ndarray, accel_fn, dt: float, nsteps: int, scheme: 
         if e < nsteps:
             x += v * dt
     return b
+
+
+# ---- the variable-step leapfrog: the fp64 specification of nbx_leaf_plan_step_kdk_adaptive (include/nbody_hip.h) ------------------
+
+def choose_step(a_max: float, accel_length: float, dt_min: float, dt_max: float, pow2: bool = False) -> float:
+    """The step the adaptive loop chooses from the largest acceleration of an evaluation: raw = sqrt(accel_length / a_max), +inf for
+    a_max == 0; clamped to [dt_min, dt_max], or with pow2 dt_max halved while it is above raw and the half is not below dt_min.  One
+    fp64 division, one square root, comparisons and exact halvings: the device's operations in the device's order."""
+    a_max, c = np.float64(a_max), np.float64(accel_length)
+    dt_min, dt_max = np.float64(dt_min), np.float64(dt_max)
+    raw = np.float64(np.inf) if a_max == 0.0 else np.sqrt(c / a_max)
+    if pow2:
+        d = dt_max
+        while d > raw and np.float64(0.5) * d >= dt_min:
+            d = np.float64(0.5) * d
+        return float(d)
+    return float(min(max(raw, dt_min), dt_max))
+
+
+def adaptive_leapfrog_spec(bodies: np.ndarray, accel_fn, control: dict, max_steps: int, in_leaf=None):
+    """nbx_leaf_plan_step_kdk_adaptive in fp64 numpy, next to leapfrog_spec and with its accel_fn.  control: a dict with accel_length,
+    dt_min, dt_max and optionally t_start (0), t_end (inf), pow2 (False).  in_leaf: a mask of the bodies that belong to a leaf (all,
+    if None); the others count 0 towards a_max, as on the device, where they have no sums.  Returns (rows, clock, history):
+    the new rows; clock, a dict with the fields of nbx_step_clock; history, an array [k, 2] of the recorded (a_max, dt).
+        t = t_start; prev = 0; steps = 0
+        for every evaluation:  a_max not finite -> status 1, stop, no kick
+                               t >= t_end or steps == max_steps -> v += a (0.5 prev); record (a_max, 0); stop
+                               dt = choose_step(a_max); landing on t_end when dt >= t_end - t
+                               v += a (0.5 prev + 0.5 dt); x += v dt; prev = dt; steps += 1; record (a_max, dt)"""
+    if max_steps < 0:
+        raise ValueError("max_steps must be >= 0")
+    c, dt_min, dt_max = (float(control[k]) for k in ("accel_length", "dt_min", "dt_max"))
+    t_start, t_end, pow2 = float(control.get("t_start", 0.0)), float(control.get("t_end", np.inf)), bool(control.get("pow2", False))
+    if not (c > 0 and np.isfinite(c) and 0 < dt_min <= dt_max and np.isfinite(dt_max) and np.isfinite(t_start)) or np.isnan(t_end) or t_end == -np.inf:
+        raise ValueError("control outside the ranges of nbx_step_control")
+    b = np.array(bodies, dtype=np.float64, copy=True)
+    dim = (b.shape[1] - 1) // 2
+    x, v = b[:, :dim], b[:, dim:2 * dim]
+    clock = {"t": t_start, "dt_last": 0.0, "a_max_last": 0.0, "steps": 0, "evaluations": 0, "finished": 0, "status": 0}
+    history = []
+    if max_steps == 0:
+        return b, clock, np.zeros((0, 2))
+    t, prev, steps = np.float64(t_start), np.float64(0.0), 0
+    half = np.float64(0.5)
+    while True:
+        a = np.asarray(accel_fn(b), dtype=np.float64)
+        mag = np.sqrt((a * a).sum(axis=1))
+        if in_leaf is not None:
+            mag = np.where(in_leaf, mag, 0.0)
+        a_max = np.float64(np.nan) if np.isnan(mag).any() else np.float64(mag.max() if mag.size else 0.0)   # a NaN orders above infinity
+        clock["evaluations"] += 1
+        clock["a_max_last"] = float(a_max)
+        if not np.isfinite(a_max):
+            clock["status"] = 1
+            break
+        if in_leaf is not None:
+            a = np.where(np.asarray(in_leaf)[:, None], a, 0.0)
+        if t >= t_end or steps == max_steps:
+            if prev != 0.0:
+                v += a * (half * prev)
+            history.append((float(a_max), 0.0))
+            clock["finished"] = 1 if t >= t_end else 0
+            break
+        dt = np.float64(choose_step(a_max, c, dt_min, dt_max, pow2))
+        if dt >= t_end - t:
+            dt, t = np.float64(t_end - t), np.float64(t_end)
+        else:
+            t = t + dt
+        v += a * (half * prev + half * dt)
+        x += v * dt
+        prev = dt
+        steps += 1
+        history.append((float(a_max), float(dt)))
+    clock.update(t=float(t), dt_last=float(prev), steps=steps)
+    return b, clock, np.array(history, dtype=np.float64).reshape(-1, 2)

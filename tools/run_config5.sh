@@ -17,6 +17,9 @@
 # A run can be cut into segments where a job may not last 1000 steps (one GPU: 3.5 s per step):
 #   METHOD=tree INTEGRATOR=kdk LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # ... with kick-drift-kick through the tree
 #                                              # (nbx_leaf_plan_step_octree_kdk): step rows with `_kdk`, synchronised energies
+#   METHOD=tree INTEGRATOR=kdka ACCEL_LENGTH=1.5 LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # ... with every step chosen
+#                                              # on the device (nbx_leaf_plan_step_kdk_adaptive): dt = sqrt(ACCEL_LENGTH / a_max) up to 0.5,
+#                                              # STEPS the cap; DT_MIN, T_END and POW2=1 as nbody_sim's --dt-min, --t-end, --pow2; rows with `_kdka`
 #   STEPS=250 DUMP=seg1 tools/run_config5.sh
 #   STEPS=250 LOAD=seg1_Leapfrog_HIP.f64 STEP_OFFSET=250 E0=<E of step 0> DUMP=seg2 tools/run_config5.sh   ... and so on;
 # k + k steps through a dump/load equal 2k steps bit for bit (tests/test_gpu_harness.py).  The state file is 56 B per body
@@ -32,7 +35,8 @@ G="${G:-0.05}"
 SOFTENING="${SOFTENING:-0}"
 LAW="${LAW:-reference}"
 METHOD="${METHOD:-brute}"            # brute = the all-pairs loop (-m g); tree = the adaptive octree on one GPU (-m t --leaf-cap 32 --far-order 1)
-INTEGRATOR="${INTEGRATOR:-kd}"       # kd = the reference helpers' order (kick, drift); kdk = synchronised leapfrog (extension)
+INTEGRATOR="${INTEGRATOR:-kd}"       # kd = the reference helpers' order (kick, drift); kdk = synchronised leapfrog (extension); kdka (METHOD=tree) = kdk, steps chosen on the device
+ACCEL_LENGTH="${ACCEL_LENGTH:-}"; DT_MIN="${DT_MIN:-}"; T_END="${T_END:-}"; POW2="${POW2:-0}"   # INTEGRATOR=kdka's control
 ENERGY="${ENERGY:-allpairs}"         # with METHOD=tree: tree = also log the energy through the tree itself (--energy-tree)
 LOAD="${LOAD:-}"; STEP_OFFSET="${STEP_OFFSET:-0}"; E0="${E0:-}"; DUMP="${DUMP:-}"
 OUT="${OUT:-gpurun_out/config5_${GPUS}gpu_${STEPS}steps.log}"
@@ -45,11 +49,20 @@ if [ -n "$DEVICES" ]; then where=(--devices "$DEVICES"); else where=(--gpus "$GP
 if [ "$ENERGY" != allpairs ] && [ "$ENERGY" != tree ]; then
     echo "ENERGY must be allpairs or tree" >&2; exit 1
 fi
+if [ "$INTEGRATOR" = kdka ] && { [ "$METHOD" != tree ] || [ -z "$ACCEL_LENGTH" ]; }; then
+    echo "INTEGRATOR=kdka needs METHOD=tree and ACCEL_LENGTH" >&2; exit 1
+fi
 if [ "$METHOD" = tree ]; then
     energy=()
     [ "$ENERGY" = tree ] && energy+=(--energy-tree)
+    if [ "$INTEGRATOR" = kdka ]; then
+        energy+=(--accel-length "$ACCEL_LENGTH")
+        [ -n "$DT_MIN" ] && energy+=(--dt-min "$DT_MIN")
+        [ -n "$T_END" ] && energy+=(--t-end "$T_END")
+        [ "$POW2" = 1 ] && energy+=(--pow2)
+    fi
     ./nbody_sim -N "$N" -d 3 -m t --leaf-cap 32 --far-order 1 --init plummer --seed 5 --G "$G" --law "$LAW" --integrator "$INTEGRATOR" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" ${energy[@]+"${energy[@]}"} | tee "$OUT"
-    grep -E "^step |Time taken|relative force error|ms per step" "$OUT" > "${OUT%.log}.summary.txt"
+    grep -E "^step |Time taken|relative force error|ms per step|^Adaptive steps" "$OUT" > "${OUT%.log}.summary.txt"
     echo "summary: ${OUT%.log}.summary.txt"
     exit 0
 elif [ "$METHOD" != brute ]; then
