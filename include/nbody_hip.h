@@ -524,6 +524,36 @@ int nbx_ctx_step(nbx_ctx* ctx, double G, double dt, int nsteps);
  * sharded form is nbx_node_step_kdk.  (nbx_ctx_step is the reference helpers' plain order, kick then drift: first order.) */
 int nbx_ctx_step_kdk(nbx_ctx* ctx, double G, double dt, int nsteps);
 
+/* EXTENSION: kick-drift-kick with the step chosen on the device, for the all-pairs context.
+ * nbx_ctx_max_accel: *a_max = max over this shard's real bodies l < count of |G| sqrt(sum_k A_k[l]^2), fp64, where A_k[l] is the
+ * fp64 sum of the context's partial sums in plane order -- after the mixed mode's fold and the close-set scatter, the number the
+ * next kick would use.  Pads never count; an empty shard gives 0; a sum that is not finite makes the result not finite.  An observer:
+ * it synchronises the stream, changes no state, and 8 bytes return.  On a multi-shard context it is this shard's maximum once this
+ * shard's sums are complete (after LOCAL + REMOTE); the caller takes the maximum over the ranks.  NBX_ERR_INVALID for a null
+ * argument, NBX_ERR_STATE without accelerations on the device.
+ * nbx_ctx_step_kdk_adaptive: nbx_ctx_step_kdk with every step's size chosen ON THE DEVICE from the evaluation just made.  It follows
+ * the rule written above for nbx_leaf_plan_step_kdk_adaptive word for word (choose, the landing on t_end, the closing half-kick,
+ * status == 1, the TIME LEVELS) with rebuild_every = 0, where "evaluate" is nbx_ctx_compute_accel(NBX_SRC_ALL), a_max is
+ * nbx_ctx_max_accel's value and the kicks are nbx_ctx_kick_drift2's arithmetic: replaying the recorded dt's with
+ * nbx_ctx_compute_accel and nbx_ctx_kick_drift2(0.5 prev + 0.5 dt, dt), then the closing nbx_ctx_kick_drift2(0.5 prev, 0), gives the
+ * same bits.  Every law, softening, dimension, precision mode and kernel variant of nbx_ctx_compute_accel; single-shard contexts
+ * only.  Asynchronous on the context's stream up to the window below.  Afterwards the context holds the accelerations of the final
+ * positions, like nbx_ctx_step_kdk; the opening evaluation is skipped when the context already holds valid ones (its reduction
+ * never is).  max_steps == 0 does nothing and leaves no clock.
+ * THE WINDOW: the host cannot know when the loop stops, and an evaluation queued behind the stop changes nothing but costs a whole
+ * all-pairs pass.  The loop therefore queues evaluation e >= W only after a 4-byte copy made behind evaluation e - W has shown that
+ * the loop had not stopped there: at most W - 1 evaluations are wasted, and the results do not depend on W.  The environment
+ * variable NBODY_HIP_STEP_WINDOW in [1, 64], read when the context is created, overrides the library's W.
+ * Refusals, before anything is launched.  NBX_ERR_INVALID (all of these need no device): a null control, a control outside the
+ * ranges given with its fields, reserved != 0, max_steps < 0 or > 1 << 20; a null context.  NBX_ERR_STATE: nothing uploaded; a
+ * context with n_shards != 1; and whatever nbx_ctx_compute_accel refuses (NBX_FORCE_LAW_NEWTON without a softening length, ...).
+ * nbx_ctx_get_step_clock / nbx_ctx_get_step_history: as nbx_leaf_plan_get_step_clock / _get_step_history, for the context's last
+ * adaptive call; NBX_ERR_STATE before the first one. */
+int nbx_ctx_max_accel(nbx_ctx* ctx, double G, double* a_max);
+int nbx_ctx_step_kdk_adaptive(nbx_ctx* ctx, double G, const nbx_step_control* control, int max_steps);
+int nbx_ctx_get_step_clock(nbx_ctx* ctx, nbx_step_clock* clock);
+int nbx_ctx_get_step_history(nbx_ctx* ctx, double* a_max_out, double* dt_out, size_t capacity, size_t* count);
+
 /* Forces of this shard's targets as Vector<dim>[count] doubles: F_i = -(G m_i) a_i.  count = this shard's bodies: shard_len, or
  * fewer -- possibly none -- for the last shards (a shard g with g * shard_len >= n_total is empty); exactly count rows are written.
  * Synchronises the stream. */

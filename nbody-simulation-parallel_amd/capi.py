@@ -87,6 +87,10 @@ ABI = [
     ("nbx_ctx_kick_drift2", _i, [_vp, _d, _d, _d]),
     ("nbx_ctx_step_kdk", _i, [_vp, _d, _d, _i]),
     ("nbx_ctx_step", _i, [_vp, _d, _d, _i]),
+    ("nbx_ctx_max_accel", _i, [_vp, _d, _pd]),
+    ("nbx_ctx_step_kdk_adaptive", _i, [_vp, _d, _vp, _i]),
+    ("nbx_ctx_get_step_clock", _i, [_vp, _vp]),
+    ("nbx_ctx_get_step_history", _i, [_vp, _vp, _vp, _sz, _c.POINTER(_sz)]),
     ("nbx_ctx_get_forces", _i, [_vp, _d, _vp]),
     ("nbx_ctx_accuracy", _i, [_vp, _d, _vp, _pd]),
     ("nbx_ctx_get_accel", _i, [_vp, _vp]),
@@ -688,6 +692,38 @@ class Context:
 
     def step(self, dt: float, nsteps: int = 1, G: float = REFERENCE_G):
         self._ck(self.lib.nbx_ctx_step(self.h, G, dt, nsteps), "nbx_ctx_step")
+
+    def max_accel(self, G: float = REFERENCE_G) -> float:
+        """The largest |acceleration| of this shard's bodies in the last evaluation, |G| |A_i|, fp64 on the device; not finite when a
+        sum is not (nbx_ctx_max_accel).  An observer: it changes no state."""
+        v = ctypes.c_double(0.0)
+        self._ck(self.lib.nbx_ctx_max_accel(self.h, float(G), ctypes.byref(v)), "nbx_ctx_max_accel")
+        return v.value
+
+    def step_kdk_adaptive(self, accel_length: float, dt_min: float, dt_max: float, t_end: float = float("inf"), max_steps: int = 1 << 20,
+                          t_start: float = 0.0, pow2: bool = False, G: float = REFERENCE_G) -> "StepClock":
+        """Kick-drift-kick with every step chosen on the device, dt = sqrt(accel_length / a_max) clamped to [dt_min, dt_max] (pow2:
+        dt_max / 2^j), until t_end or max_steps (nbx_ctx_step_kdk_adaptive).  Returns the clock (which synchronises)."""
+        k = StepControl(float(accel_length), float(dt_min), float(dt_max), float(t_start), float(t_end), 1 if pow2 else 0, 0)
+        self._ck(self.lib.nbx_ctx_step_kdk_adaptive(self.h, float(G), ctypes.byref(k), int(max_steps)), "nbx_ctx_step_kdk_adaptive")
+        return self.step_clock() if int(max_steps) > 0 else None
+
+    def step_clock(self) -> "StepClock":
+        """The device's clock as the last adaptive call left it (nbx_ctx_get_step_clock); synchronises."""
+        k = StepClock()
+        self._ck(self.lib.nbx_ctx_get_step_clock(self.h, ctypes.byref(k)), "nbx_ctx_get_step_clock")
+        return k
+
+    def step_history(self):
+        """(a_max[k], dt[k]) of the evaluations the last adaptive call recorded, oldest first; the closing evaluation's dt is 0
+        (nbx_ctx_get_step_history)."""
+        count = ctypes.c_size_t(0)
+        self._ck(self.lib.nbx_ctx_get_step_history(self.h, None, None, 0, ctypes.byref(count)), "nbx_ctx_get_step_history")
+        a, dt = np.zeros(count.value, dtype=np.float64), np.zeros(count.value, dtype=np.float64)
+        if count.value:
+            self._ck(self.lib.nbx_ctx_get_step_history(self.h, a.ctypes.data, dt.ctypes.data, count.value, ctypes.byref(count)),
+                     "nbx_ctx_get_step_history")
+        return a, dt
 
     def forces(self, G: float = REFERENCE_G) -> np.ndarray:
         out = np.empty((self.count, self.dim), dtype=np.float64)

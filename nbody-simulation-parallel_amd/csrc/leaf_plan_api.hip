@@ -1033,17 +1033,6 @@ int nbx_leaf_plan_step_octree_kdk(nbx_leaf_plan* p, nbx_ctx* c, int law, double 
 }
 
 // ---- kick-drift-kick with the step chosen on the device (include/nbody_hip.h has the rule; state_kernels.hip the controller) ----
-static const char* step_control_fault(const nbx_step_control* k) {
-    if (!(k->accel_length > 0.0) || !std::isfinite(k->accel_length)) return "accel_length must be finite and > 0";
-    if (!(k->dt_min > 0.0) || !std::isfinite(k->dt_min)) return "dt_min must be finite and > 0";
-    if (!(k->dt_max >= k->dt_min) || !std::isfinite(k->dt_max)) return "dt_max must be finite and >= dt_min";
-    if (!std::isfinite(k->t_start)) return "t_start must be finite";
-    if (std::isnan(k->t_end) || (std::isinf(k->t_end) && k->t_end < 0.0)) return "t_end must be finite or +infinity";
-    if (k->pow2 != 0 && k->pow2 != 1) return "pow2 must be 0 or 1";
-    if (k->reserved != 0) return "reserved must be 0";
-    return nullptr;
-}
-
 constexpr int kStopLookEvery = 16;   // evaluations between two looks at the clock's `stopped` (the context's close-set look's spacing)
 
 // The step clock's block with room for a call of max_steps steps, and what the loop's looks need.  Growing the block waits for

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -113,6 +114,17 @@ std::mutex g_ctx_mu;
 std::vector<unsigned long long> g_live_ctx;
 std::atomic<unsigned long long> g_next_ctx_id{1};
 }  // namespace
+const char* step_control_fault(const nbx_step_control* k) {
+    if (!(k->accel_length > 0.0) || !std::isfinite(k->accel_length)) return "accel_length must be finite and > 0";
+    if (!(k->dt_min > 0.0) || !std::isfinite(k->dt_min)) return "dt_min must be finite and > 0";
+    if (!(k->dt_max >= k->dt_min) || !std::isfinite(k->dt_max)) return "dt_max must be finite and >= dt_min";
+    if (!std::isfinite(k->t_start)) return "t_start must be finite";
+    if (std::isnan(k->t_end) || (std::isinf(k->t_end) && k->t_end < 0.0)) return "t_end must be finite or +infinity";
+    if (k->pow2 != 0 && k->pow2 != 1) return "pow2 must be 0 or 1";
+    if (k->reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
 bool ctx_alive(unsigned long long id) {
     std::lock_guard<std::mutex> lock(g_ctx_mu);
     for (unsigned long long v : g_live_ctx) if (v == id) return true;
@@ -148,6 +160,9 @@ constexpr int kMaxSplits = 256;
 #define NBX_SYM_DEFAULT 0
 #endif
 constexpr int kPhiSlices = 16;
+// nbx_ctx_step_kdk_adaptive queues at most this many evaluations ahead of its looks at the clock's `stopped`, so at most this many
+// less one are wasted behind the stop (DESIGN.md section 3 has the measurement; NBODY_HIP_STEP_WINDOW in [1, kStepWindowMax] overrides)
+constexpr int kStepWindowDefault = 2;
 constexpr int kGraphMinSteps = 4;   // nbx_ctx_step replays a captured step from this many steps on
 // Mixed mode: selection rule |a|^2 < (sigma u / tol)^2 Q (force_kernel.hip).  The sigma factor is a calibration of the DEFAULT
 // kernel's summation (round 4: the three-level kernel, whose rounding errors are ~3x smaller than the two-level kernel's at the same
@@ -435,6 +450,20 @@ int poll_close_counters(nbx_ctx* c, int steps) {
     return NBX_OK;
 }
 
+// What nbx_ctx_compute_accel refuses about the law, the softening and the masses (decided on the host, before any launch).
+int law_refusal(const nbx_ctx* c) {
+    const float eps2 = (float)(c->softening * c->softening);
+    if (c->law != 0 && !(c->softening > 0.0)) return fail(NBX_ERR_STATE, "the Newtonian law needs a softening length (nbx_ctx_set_softening)");
+    if (c->softening > 0.0 && !(c->mass_max / ((double)eps2 * (double)eps2) < 1.0e38))
+        return fail(NBX_ERR_INVALID, "softening too small for these masses: m / eps^4 must stay finite in fp32");
+    // ... and too LARGE a softening length makes every pair weight underflow to zero in fp32 (the result would be an
+    // all-zero force field with status OK): the heaviest body's weight at zero distance must be a normal fp32 number
+    if (c->softening > 0.0 && c->mass_max > 0.0 &&
+        !(c->mass_max / (c->law ? (double)eps2 * c->softening : (double)eps2 * (double)eps2) > 1.0e-30))
+        return fail(NBX_ERR_INVALID, "softening too large for these masses: m / eps^4 (Newtonian law: m / eps^3) underflows in fp32");
+    return NBX_OK;
+}
+
 int set_device(const nbx_ctx* c) {
     (void)hipGetLastError();  // launches are checked with hipGetLastError(): start from a clean slate
     HIP_TRY(hipSetDevice(c->device));
@@ -636,6 +665,13 @@ int nbx_ctx_create(nbx_ctx** out, int device, int dim, size_t n_total, int n_sha
     c->refine_tol = g_default_refine_tol.load();       // mixed mode unless the process default says plain fp32
     c->refine_sigma = g_default_refine_sigma.load();
     { const char* e = std::getenv("NBODY_HIP_NO_GRAPHS"); c->no_graphs = e && *e && *e != '0'; }
+    {
+        c->step_window = kStepWindowDefault;
+        const char* e = std::getenv("NBODY_HIP_STEP_WINDOW");
+        char* end = nullptr;
+        const long w = e && *e ? std::strtol(e, &end, 10) : 0;
+        if (end && *end == '\0' && w >= 1 && w <= kStepWindowMax) c->step_window = (int)w;
+    }
 #define CTX_TRY(expr)                                                            \
     do {                                                                         \
         hipError_t e_ = (expr);                                                  \
@@ -695,6 +731,10 @@ int nbx_ctx_destroy(nbx_ctx* c) {
         if (idle) nbx_block::ctx_pool().park(c->device, c->arena, c->arena_bytes);
         else (void)hipFree(c->arena);
     }
+    if (c->clock_block) (void)hipFree(c->clock_block);
+    if (c->amax_word) (void)hipFree(c->amax_word);
+    if (c->stop_ring) (void)hipHostFree(c->stop_ring);
+    for (auto e : c->stop_ev) if (e) (void)hipEventDestroy(e);
     if (c->counters_host) (void)hipHostFree(c->counters_host);
     if (c->counters_ev) (void)hipEventDestroy(c->counters_ev);
     if (c->step_exec) (void)hipGraphExecDestroy(c->step_exec);
@@ -960,14 +1000,7 @@ int nbx_ctx_compute_accel(nbx_ctx* c, int which) {
     }
     L.qsum = (refine || variant_writes_aux(c->variant)) ? c->qsum : nullptr;
     if (c->hash_refine && variant_is_fast(c->variant) && !(c->softening > 0.0)) L.hash = c->hash;
-    if (c->law != 0 && !(c->softening > 0.0)) return fail(NBX_ERR_STATE, "the Newtonian law needs a softening length (nbx_ctx_set_softening)");
-    if (c->softening > 0.0 && !(c->mass_max / ((double)L.eps2 * (double)L.eps2) < 1.0e38))
-        return fail(NBX_ERR_INVALID, "softening too small for these masses: m / eps^4 must stay finite in fp32");
-    // ... and too LARGE a softening length makes every pair weight underflow to zero in fp32 (the result would be an
-    // all-zero force field with status OK): the heaviest body's weight at zero distance must be a normal fp32 number
-    if (c->softening > 0.0 && c->mass_max > 0.0 &&
-        !(c->mass_max / (c->law ? (double)L.eps2 * c->softening : (double)L.eps2 * (double)L.eps2) > 1.0e-30))
-        return fail(NBX_ERR_INVALID, "softening too large for these masses: m / eps^4 (Newtonian law: m / eps^3) underflows in fp32");
+    if (int lrc = law_refusal(c)) return lrc;
     L.chunk_skip = INT_MAX; L.accumulate = 0;
     if (which == NBX_SRC_ALL) { L.chunk_first = 0; L.vchunks = c->n_shards; }
     else if (which == NBX_SRC_LOCAL) { L.chunk_first = c->shard; L.vchunks = 1; }
@@ -1133,6 +1166,137 @@ int nbx_ctx_step_kdk(nbx_ctx* c, double G, double dt, int nsteps) {
     }
     if (!rc) rc = nbx_ctx_kick_drift2(c, G, 0.5 * dt, 0.0);
     return rc;
+}
+
+// ---- kick-drift-kick with the step chosen on the device (include/nbody_hip.h has the rule; state_kernels.hip the kernels) ----
+// An observer: it reads the planes and writes its own 8-byte word.
+int nbx_ctx_max_accel(nbx_ctx* c, double G, double* a_max) {
+    if (!c || !a_max) return fail(NBX_ERR_INVALID, "null argument");
+    if (!c->have_accel) return fail(NBX_ERR_STATE, "no accelerations computed");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if (!c->amax_word) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->amax_word), 256));
+    HIP_TRY(launch_ctx_accel_max(c->acc, c->splits, c->dim, c->pad, c->count, std::fabs(G), c->amax_word, c->stream));
+    unsigned long long bits = 0ull;
+    HIP_TRY(hipMemcpyAsync(&bits, c->amax_word, sizeof bits, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(a_max, &bits, sizeof bits);
+    return NBX_OK;
+}
+
+// The step clock's block with room for a call of max_steps steps, and what the loop's looks need.  Growing the block waits for
+// the context's queued work first: an earlier call's kernels may still read the one held.
+static int ctx_fit_clock(nbx_ctx* c, int max_steps) {
+    const size_t need = kStepClockHistoryOffset + ((size_t)max_steps + 1) * 2 * sizeof(double);
+    if (c->clock_bytes < need) {
+        if (c->clock_block) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(hipFree(c->clock_block));
+            c->clock_block = nullptr; c->clock_bytes = 0;
+        }
+        c->clock_valid = false;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->clock_block), need));
+        c->clock_bytes = need;
+    }
+    if (!c->stop_ring) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->stop_ring), kStepWindowMax * sizeof(int), hipHostMallocDefault));
+    if (c->stop_ev.empty()) c->stop_ev.assign(kStepWindowMax, nullptr);
+    return NBX_OK;
+}
+
+// nbx_ctx_step_kdk with every kick read from the clock.  Per evaluation e = 0 .. max_steps the stream gets: the force launch (and
+// the mixed mode's refinement), the memset of the maximum's word, the reduction, the controller, the clock kick.  The host knows
+// neither the steps' sizes nor when the loop stops, so around every clock kick it does a drifting nbx_ctx_kick_drift2's bookkeeping;
+// what it queues behind the stop changes nothing (the positions stand, so the sums come out the same; the controller records nothing
+// and the kick is not applied) but costs a whole evaluation -- up to 230 ms here.  So behind every clock kick goes a 4-byte copy of
+// `stopped` into a ring of pinned words, with an event, and evaluation e >= W is queued only once the look behind evaluation e - W
+// has landed and shows no stop: at most W - 1 evaluations are wasted, and W = 1 is the synchronous loop.
+int nbx_ctx_step_kdk_adaptive(nbx_ctx* c, double G, const nbx_step_control* control, int max_steps) {
+    // what needs no device first: the control and the count, then the handle
+    if (!control) return fail(NBX_ERR_INVALID, "null argument");
+    if (const char* why = step_control_fault(control)) return fail(NBX_ERR_INVALID, why);
+    if (max_steps < 0 || max_steps > (1 << 20)) return fail(NBX_ERR_INVALID, "max_steps must be in [0, 1 << 20]");
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies before stepping");
+    if (c->n_shards != 1) return fail(NBX_ERR_STATE, "nbx_ctx_step_kdk_adaptive drives single-shard contexts only");
+    if (int lrc = law_refusal(c)) return lrc;
+    if (max_steps == 0) return NBX_OK;
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = ctx_fit_clock(c, max_steps))) return rc;
+    StepClock* const clock = reinterpret_cast<StepClock*>(c->clock_block);
+    hipStream_t s = c->stream;
+    HIP_TRY(launch_step_clock_init(clock, control->accel_length, control->dt_min, control->dt_max, control->t_start, control->t_end, control->pow2,
+                                   (uint32_t)max_steps + 1u, s));
+    c->clock_valid = true;
+    const int W = c->step_window;
+    for (int e = 0; e <= max_steps; ++e) {
+        if (e >= W) {
+            const int seen = (e - W) % kStepWindowMax;
+            HIP_TRY(hipEventSynchronize(c->stop_ev[seen]));
+            if (c->stop_ring[seen]) break;   // stopped at or before evaluation e - W: the sums on the device are the final positions'
+        }
+        if (e > 0) {                         // the kick of evaluation e - 1 may have drifted
+            c->have_accel = false;
+            c->tgt_cand_valid = 0; c->bad_list_pass = -1;
+        }
+        if (!c->have_accel && (rc = nbx_ctx_compute_accel(c, NBX_SRC_ALL))) return rc;
+        HIP_TRY(launch_ctx_accel_max(c->acc, c->splits, c->dim, c->pad, c->count, std::fabs(G), &clock->amax_bits, s));
+        HIP_TRY(launch_step_control(clock, e == max_steps, s));
+        if ((rc = poll_close_counters(c, 1))) return rc;   // as a drifting nbx_ctx_kick_drift2: the counters belong to this step
+        KickDriftArgs k;
+        k.acc = c->acc; k.splits = c->splits; k.dim = c->dim; k.pad = c->pad; k.count = c->count; k.G = c->law ? -G : G;
+        k.dt_kick = 0.0; k.dt_drift = 0.0;
+        k.x64 = c->x64; k.v64 = c->v64; k.m64 = c->m64;
+        k.pos_chunk = c->pos_all + (size_t)c->shard * c->dim * c->pad;
+        HIP_TRY(launch_kick_drift_clock(k, clock, s));
+        const int slot = e % kStepWindowMax;
+        if (!c->stop_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&c->stop_ev[slot], hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(&c->stop_ring[slot], &clock->stopped, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(c->stop_ev[slot], s));
+    }
+    // the last evaluation queued is the stopping one or lies behind it: its kick did not drift, its sums are the final positions'
+    return NBX_OK;
+}
+
+static int ctx_read_clock(nbx_ctx* c, StepClock* host) {
+    HIP_TRY(hipMemcpyAsync(host, c->clock_block, sizeof(StepClock), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return NBX_OK;
+}
+
+int nbx_ctx_get_step_clock(nbx_ctx* c, nbx_step_clock* out) {
+    if (!c || !out) return fail(NBX_ERR_INVALID, "null argument");
+    if (!c->clock_valid) return fail(NBX_ERR_STATE, "no adaptive call on this context yet (nbx_ctx_step_kdk_adaptive)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    StepClock k;
+    if ((rc = ctx_read_clock(c, &k))) return rc;
+    out->t = k.t; out->dt_last = k.prev; out->a_max_last = k.a_max_last;
+    out->steps = k.steps; out->evaluations = k.evaluations;
+    out->finished = k.finished; out->status = k.status;
+    return NBX_OK;
+}
+
+int nbx_ctx_get_step_history(nbx_ctx* c, double* a_max_out, double* dt_out, size_t capacity, size_t* count) {
+    if (!c || !count) return fail(NBX_ERR_INVALID, "null argument");
+    if (!c->clock_valid) return fail(NBX_ERR_STATE, "no adaptive call on this context yet (nbx_ctx_step_kdk_adaptive)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    StepClock k;
+    if ((rc = ctx_read_clock(c, &k))) return rc;
+    *count = k.recorded;
+    const size_t take = capacity < (size_t)k.recorded ? capacity : (size_t)k.recorded;
+    if (take && (a_max_out || dt_out)) {
+        std::vector<double> pairs;
+        try { pairs.resize(2 * take); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
+        HIP_TRY(hipMemcpyAsync(pairs.data(), c->clock_block + kStepClockHistoryOffset, 2 * take * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < take; ++i) {
+            if (a_max_out) a_max_out[i] = pairs[2 * i];
+            if (dt_out) dt_out[i] = pairs[2 * i + 1];
+        }
+    }
+    return NBX_OK;
 }
 
 int nbx_ctx_get_forces(nbx_ctx* c, double G, double* out) {

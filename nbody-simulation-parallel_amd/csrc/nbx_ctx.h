@@ -7,6 +7,8 @@
 
 #include "nbx_internal.h"
 
+struct nbx_step_control;   // include/nbody_hip.h
+
 struct nbx_ctx {
     unsigned long long id = 0;   // unique per context ever created in this process (never reused: a leaf plan remembers WHICH context its last evaluation read, not where it lived)
     int device = 0, dim = 3, n_shards = 1, shard = 0;
@@ -104,6 +106,14 @@ struct nbx_ctx {
     unsigned clk_slots = 0;              // workgroups of the last stamped launch
     unsigned long long* graph_clk = nullptr;   // the stamp buffer baked into the captured step (null: none)
     int num_cus = 256;
+    // the step clock (nbx_ctx_step_kdk_adaptive; nbx_internal.h: StepClock): its own allocation, made by the first adaptive call
+    char* clock_block = nullptr;     // the clock and, kStepClockHistoryOffset behind it, the history of the last call
+    size_t clock_bytes = 0;
+    bool clock_valid = false;        // an adaptive call has gone through: the block holds its clock
+    int step_window = 0;             // evaluations the loop queues ahead of its looks at the clock's `stopped` (NBODY_HIP_STEP_WINDOW)
+    int* stop_ring = nullptr;        // pinned [kStepWindowMax]: the look behind evaluation e lands in word e % kStepWindowMax ...
+    std::vector<hipEvent_t> stop_ev; // ... and this event says that it has
+    unsigned long long* amax_word = nullptr;   // nbx_ctx_max_accel's 8-byte word, its own allocation, made when a caller first asks
 };
 
 namespace nbx {
@@ -121,6 +131,9 @@ void release_parked_streams();
 int upload_stage(nbx_ctx* c, const void* bodies, size_t stride_bytes, bool only_own, unsigned long long facts[3],
                  bool bodies_is_own_slice = false);   // true: `bodies` points at this shard's first body, not at body 0
 int upload_finish(nbx_ctx* c, const unsigned long long facts[3]);
+// why a step control is refused, or null (nbx_api.hip; the plan's and the context's adaptive loops share it): needs no device
+const char* step_control_fault(const nbx_step_control* k);
+constexpr int kStepWindowMax = 64;
 bool ctx_alive(unsigned long long id);  // nbx_api.hip: a context with this id exists (created, not yet destroyed)
 void release_parked_communicators();   // nbx_node.hip
 }  // namespace nbx

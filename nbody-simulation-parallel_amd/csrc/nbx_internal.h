@@ -300,6 +300,15 @@ hipError_t launch_step_controller(const double* sums, const uint32_t* pslot_body
                                   hipStream_t stream);
 // launch_kick_drift_slots with dt_kick, dt_drift and the two flags read from the clock (k's own are not read)
 hipError_t launch_kick_drift_slots_clock(const SlotKickArgs& k, const StepClock* clock, hipStream_t stream);
+// The same loop for the all-pairs context (nbx_ctx_step_kdk_adaptive), whose sums are the fp32 planes of KickDriftArgs:
+// *out (device, 8 bytes; zeroed here first) = bit pattern of max over the count real bodies of absG * |A[l]|, A_k[l] the fp64 sum of
+// the planes in plane order (kick_drift_kernel's sum_partials, bit for bit); a sum that is not finite makes it not finite
+hipError_t launch_ctx_accel_max(const float* acc, int splits, int dim, unsigned pad, size_t count, double absG, unsigned long long* out,
+                                hipStream_t stream);
+// the controller alone, behind whichever reduction has filled clock->amax_bits (launch_step_controller = the plan's reduction + this)
+hipError_t launch_step_control(StepClock* clock, bool last, hipStream_t stream);
+// launch_kick_drift with dt_kick and dt_drift read from the clock (k's own are not read); nothing is touched when clock->apply == 0
+hipError_t launch_kick_drift_clock(const KickDriftArgs& k, const StepClock* clock, hipStream_t stream);
 
 // forces_out: AoS double[count][dim] on the device
 hipError_t launch_export_forces(const float* acc, int splits, int dim, unsigned pad, size_t count,

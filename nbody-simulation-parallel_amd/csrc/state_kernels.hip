@@ -257,6 +257,67 @@ __global__ __launch_bounds__(256) void kick_drift_slots_clock_kernel(SlotKickArg
     }
 }
 
+// ---- the same loop for the all-pairs context (nbx_ctx_step_kdk_adaptive) ----
+// The largest acceleration of the context's last evaluation: max over the real bodies l < count of absG * sqrt(sum_k A_k[l]^2), A_k[l]
+// = sum_partials, the very number kick_drift_kernel is about to use (same loop, same load batching, plane order: same bits).  It
+// streams 4 * DIM * splits bytes per body and writes nothing but the word.  One lane per (body, component), as kick_drift_kernel and
+// for its reason -- one lane per body is a chain of DIM * splits dependent-address loads, 25 us at N = 65,536 -- with threadIdx.y the
+// component: a wave is 64 consecutive bodies of ONE component (a 256-byte row per plane), the DIM squares of a body meet in LDS and
+// are added in component order by the lanes of component 0.  The maximum is pack_kernel's idiom: bit patterns of non-negative
+// doubles (a NaN's lies above infinity's: a sum that is not finite makes the result not finite), butterfly over the wave, one LDS
+// atomic per wave that holds bodies, one L2 atomic per workgroup.  Every lane stays for the shuffles; pads never count.
+template <int DIM>
+__global__ __launch_bounds__(256 * DIM) void ctx_accel_max_kernel(const float* __restrict__ acc, int splits, unsigned pad, size_t count,
+                                                                  double absG, unsigned long long* __restrict__ out) {
+    __shared__ double s_sq[DIM][256];
+    __shared__ unsigned long long s_max;
+    if (threadIdx.x == 0 && threadIdx.y == 0) s_max = 0ull;
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int k = (int)threadIdx.y;
+    double sq = 0.0;
+    if (l < count) {
+        const double s = sum_partials(acc, splits, DIM, pad, k, l);
+        sq = s * s;
+    }
+    s_sq[k][threadIdx.x] = sq;
+    __syncthreads();
+    unsigned long long ab = 0ull;
+    if (k == 0 && l < count) {
+        double s2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) s2 += s_sq[j][threadIdx.x];
+        ab = (unsigned long long)__double_as_longlong(fabs(absG * sqrt(s2)));   // fabs: a NaN's sign bit goes too
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(ab, off);
+        ab = o > ab ? o : ab;
+    }
+    if (k == 0 && (threadIdx.x & 63u) == 0u && ab) atomicMax(&s_max, ab);
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0 && s_max > *(volatile unsigned long long*)out) atomicMax(out, s_max);
+}
+
+// kick_drift_kernel's body with dt_kick and dt_drift read from the clock (uniform addresses, the same for every lane): given the
+// same two numbers, the same bits.  apply == 0 (the loop has stopped, or a closing kick of nothing): nothing is read or written.
+__global__ __launch_bounds__(256) void kick_drift_clock_kernel(KickDriftArgs a, const StepClock* __restrict__ clock) {
+    if (clock->apply == 0) return;
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= a.count) return;
+    const double dt_kick = clock->dt_kick, dt_drift = clock->dt_drift;
+    const int k = (int)blockIdx.y;
+    const double m = a.m64[l];
+    const double gm = a.G * m;
+    const double acc = sum_partials(a.acc, a.splits, a.dim, a.pad, k, l);
+    const double F = -(gm * acc);
+    double v = a.v64[(size_t)k * a.pad + l];
+    double x = a.x64[(size_t)k * a.pad + l];
+    v += (F / m) * dt_kick;
+    x += v * dt_drift;
+    a.v64[(size_t)k * a.pad + l] = v;
+    a.x64[(size_t)k * a.pad + l] = x;
+    a.pos_chunk[(size_t)k * a.pad + l] = (float)x;
+}
+
 __global__ __launch_bounds__(256) void export_forces_kernel(const float* __restrict__ acc, int splits, int dim,
                                                             unsigned pad, size_t count, double G,
                                                             const double* __restrict__ m64,
@@ -398,7 +459,26 @@ hipError_t launch_step_controller(const double* sums, const uint32_t* pslot_body
         hipLaunchKernelGGL(slot_accel_max_by_slot_kernel, dim3(blocks_for(pslots)), dim3(256), 0, stream, sums, pslot_body, pslots, dim, absG, &clock->amax_bits);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    return launch_step_control(clock, last, stream);
+}
+
+hipError_t launch_step_control(StepClock* clock, bool last, hipStream_t stream) {
     hipLaunchKernelGGL(step_controller_kernel, dim3(1), dim3(64), 0, stream, clock, last ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctx_accel_max(const float* acc, int splits, int dim, unsigned pad, size_t count, double absG, unsigned long long* out,
+                                hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess || count == 0) return e;
+    if (dim == 2) hipLaunchKernelGGL(ctx_accel_max_kernel<2>, dim3(blocks_for(count)), dim3(256, 2, 1), 0, stream, acc, splits, pad, count, absG, out);
+    else hipLaunchKernelGGL(ctx_accel_max_kernel<3>, dim3(blocks_for(count)), dim3(256, 3, 1), 0, stream, acc, splits, pad, count, absG, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_kick_drift_clock(const KickDriftArgs& k, const StepClock* clock, hipStream_t stream) {
+    if (k.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(kick_drift_clock_kernel, dim3(blocks_for(k.count), (unsigned)k.dim, 1), dim3(256), 0, stream, k, clock);
     return hipGetLastError();
 }
 

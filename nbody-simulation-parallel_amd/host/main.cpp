@@ -625,13 +625,19 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
     }
 
     if (opt.steps > 0 && run_hip) {
-        out << "Leapfrog (kick-drift) on HIP: " << opt.steps << " steps, dt = " << opt.dt << ", G = " << opt.G;
+        out << "Leapfrog (kick-drift) on HIP: " << opt.steps << " steps" << (opt.integrator == "kdka" ? " at most (steps chosen on the device)" : "") << ", dt = " << opt.dt << ", G = " << opt.G;
         if (opt.softening > 0.0) out << ", softening = " << opt.softening;
         if (opt.law != "reference") out << ", law = " << opt.law;
         if (opt.integrator != "kd") out << ", integrator = " << opt.integrator;
         out << std::endl;
         std::vector<Body<D>> state = bodies;
         double kernel_s = 0.0;
+        // --integrator kdka: chained calls of --energy-every steps with every step chosen on the device (nbx_ctx_step_kdk_adaptive), each
+        // starting at the t the one before reached; the row carries `_kdka` and a line behind the loop gives the steps taken and the range of dt
+        const bool ctx_kdka = opt.integrator == "kdka";
+        nbx_step_clock ctx_clock{};
+        double ctx_dt_smallest = 0.0, ctx_dt_largest = 0.0;
+        unsigned ctx_taken = 0;
         const long long us = safely_execute(log, "Leapfrog_HIP", [&] {
             HipSimulation<D> sim(bodies, opt.G, opt.softening, opt.law == "newton");
             double ke = 0.0, pe = 0.0, e0 = 0.0;
@@ -645,13 +651,29 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
             }
             for (int done = 0; done < opt.steps;) {
                 const int k = std::min(chunk, opt.steps - done);
-                if (opt.integrator == "kdk") sim.step_kdk(opt.dt, k); else sim.step(opt.dt, k);
-                done += k;
+                if (ctx_kdka) {   // chained calls of k steps: each ends synchronised, the next starts at its t
+                    nbx_step_control control = chosen.control;
+                    control.t_start = ctx_taken ? ctx_clock.t : control.t_start;
+                    ctx_clock = sim.step_kdk_adaptive(control, k);
+                    double lo = 0.0, hi = 0.0;
+                    sim.step_range(lo, hi);
+                    if (lo > 0.0) ctx_dt_smallest = ctx_dt_smallest > 0.0 ? std::min(ctx_dt_smallest, lo) : lo;
+                    ctx_dt_largest = std::max(ctx_dt_largest, hi);
+                    ctx_taken += ctx_clock.steps;
+                    done += static_cast<int>(ctx_clock.steps);
+                    if (ctx_clock.finished || ctx_clock.status || ctx_clock.steps == 0) done = opt.steps;   // the last energy line, then out
+                    ctx_clock.steps = ctx_taken;
+                } else {
+                    if (opt.integrator == "kdk") sim.step_kdk(opt.dt, k); else sim.step(opt.dt, k);
+                    done += k;
+                }
                 if (opt.energy_every > 0) {
                     sim.energy(ke, pe);
-                    out << "step " << opt.step_offset + done << "  E = " << std::setprecision(12) << ke + pe << "  |dE/E0| = " << std::setprecision(3)
+                    out << "step " << opt.step_offset + (ctx_kdka ? static_cast<int>(ctx_taken) : done) << "  E = " << std::setprecision(12) << ke + pe << "  |dE/E0| = " << std::setprecision(3)
                         << std::abs((ke + pe - e0) / e0) << std::setprecision(6) << "  (kinetic " << ke << ", potential " << pe
-                        << ", 2K/|U| " << 2.0 * ke / std::abs(pe) << ")" << std::endl;
+                        << ", 2K/|U| " << 2.0 * ke / std::abs(pe) << ")";
+                    if (ctx_kdka) out << "  t = " << std::setprecision(12) << ctx_clock.t << std::setprecision(6);
+                    out << std::endl;
                 }
             }
             sim.download(state);
@@ -660,11 +682,12 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
         });
         if (us >= 0) {
             const double seconds = static_cast<double>(us) / 1e6;
-            csv << "Leapfrog_HIP_" << opt.steps << "steps," << n << "," << D;
+            csv << "Leapfrog_HIP_" << opt.steps << "steps" << (ctx_kdka ? "_kdka" : "") << "," << n << "," << D;
             write_time(csv, seconds);
             if (opt.accuracy) csv << ",";
             csv << std::endl;
             out << "Time taken: " << seconds << " s (" << seconds / opt.steps << " s/step; force kernels " << kernel_s << " s per rank)" << std::endl;
+            if (ctx_kdka) adaptive_line(ctx_clock.steps, ctx_clock.t, ctx_dt_smallest, ctx_dt_largest, ctx_clock.finished != 0);
             if (!opt.dump.empty()) dump_raw(opt.dump + "_Leapfrog_HIP.f64", state);
             out << "Body #1 position: (";
             for (int d = 0; d < D; ++d) out << state[0].position[d] << (d < D - 1 ? ", " : "");
@@ -695,7 +718,7 @@ void usage(const char* argv0) {
               << "      --integrator <kd|kdk> kd = update_body_velocities then update_body_positions per step (default, first order);" << std::endl
               << "                      kdk = the same helpers as a synchronised kick-drift-kick leapfrog (extension, second order)" << std::endl
               << "                      with -m t: the tree's step loops run kick-drift-kick too and their rows carry _kdk" << std::endl
-              << "                      kdka (-m t alone) = kick-drift-kick with every step chosen on the device, dt = sqrt(c / a_max) from the largest" << std::endl
+              << "                      kdka (-m t, or -m g on one GPU) = kick-drift-kick with every step chosen on the device, dt = sqrt(c / a_max) from the largest" << std::endl
               << "                      acceleration of the evaluation just made; --dt is the largest step, --steps the cap, rows carry _kdka" << std::endl
               << "      --accel-length <c> kdka's c (a length: eta^2 x softening is the usual choice); --dt-min <t> its smallest step (default --dt / 1024);" << std::endl
               << "                      --t-end <t> where it stops (default: after --steps steps); --pow2: its steps are --dt / 2^j" << std::endl
@@ -846,8 +869,12 @@ int main(int argc, char* argv[]) {
     }
 
     if (opt.integrator == "kdka") {
-        if (opt.methods.empty() || opt.methods.find_first_of("ag") != std::string::npos) {
-            std::cerr << "Error: --integrator kdka is the tree's step loop: use it with -m t" << std::endl;
+        if (opt.methods.empty() || opt.methods.find('a') != std::string::npos) {
+            std::cerr << "Error: --integrator kdka drives the tree's step loops (-m t) and the all-pairs loop on one GPU (-m g)" << std::endl;
+            return 1;
+        }
+        if (opt.methods.find('g') != std::string::npos && opt.devices.size() > 1) {
+            std::cerr << "Error: --integrator kdka with -m g runs on one GPU: leave --gpus / --devices out (the sharded loop has no steps chosen on the device)" << std::endl;
             return 1;
         }
         if (!(opt.accel_length > 0.0)) {

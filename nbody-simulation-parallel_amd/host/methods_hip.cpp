@@ -1,6 +1,7 @@
 // methods_hip.cpp -- thin C++ shim from the reference-shaped templates onto the C ABI.
 #include "methods_hip.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
@@ -184,44 +185,116 @@ template <int D>
 HipSimulation<D>::HipSimulation(const std::vector<Body<D>>& bodies, double G, double softening, bool newton) : G_(G) {
     std::vector<int> devs = g_devices.empty() ? std::vector<int>{device_ordinal()} : g_devices;
     ranks_ = (int)devs.size();
-    int rc = nbx_node_create(&node_, ranks_, devs.data(), D, bodies.size(), NBX_EXCHANGE_AUTO);
-    if (!rc) rc = nbx_node_upload_bodies(node_, bodies.data(), sizeof(Body<D>));
-    if (!rc && softening != 0.0) rc = nbx_node_set_softening(node_, softening);
-    if (!rc && newton) rc = nbx_node_set_law(node_, NBX_FORCE_LAW_NEWTON);
+    int rc = NBX_OK;
+    if (ranks_ == 1) {
+        rc = nbx_ctx_create(&ctx_, devs[0], D, bodies.size(), 1, 0);
+        if (!rc) rc = nbx_ctx_upload_bodies(ctx_, bodies.data(), sizeof(Body<D>));
+        if (!rc && softening != 0.0) rc = nbx_ctx_set_softening(ctx_, softening);
+        if (!rc && newton) rc = nbx_ctx_set_law(ctx_, NBX_FORCE_LAW_NEWTON);
+    } else {
+        rc = nbx_node_create(&node_, ranks_, devs.data(), D, bodies.size(), NBX_EXCHANGE_AUTO);
+        if (!rc) rc = nbx_node_upload_bodies(node_, bodies.data(), sizeof(Body<D>));
+        if (!rc && softening != 0.0) rc = nbx_node_set_softening(node_, softening);
+        if (!rc && newton) rc = nbx_node_set_law(node_, NBX_FORCE_LAW_NEWTON);
+    }
     if (rc != NBX_OK) {
         nbx_node_destroy(node_);
+        nbx_ctx_destroy(ctx_);
         node_ = nullptr;
+        ctx_ = nullptr;
         raise("HipSimulation", rc);
     }
 }
 template <int D>
-HipSimulation<D>::~HipSimulation() { nbx_node_destroy(node_); }
+HipSimulation<D>::~HipSimulation() {
+    nbx_node_destroy(node_);
+    nbx_ctx_destroy(ctx_);
+}
+// One device: the calls of a one-rank node, one by one (an evaluation over all sources, then the kick), so the bits are the node's.
 template <int D>
 void HipSimulation<D>::step(double dt, int nsteps) {
-    const int rc = nbx_node_step(node_, G_, dt, nsteps);
+    int rc = NBX_OK;
+    if (ctx_) {
+        if (nsteps < 0) rc = NBX_ERR_INVALID;
+        for (int s = 0; s < nsteps && !rc; ++s) {
+            rc = nbx_ctx_compute_accel(ctx_, NBX_SRC_ALL);
+            if (!rc) rc = nbx_ctx_kick_drift(ctx_, G_, dt);
+        }
+    } else {
+        rc = nbx_node_step(node_, G_, dt, nsteps);
+    }
     if (rc != NBX_OK) raise("HipSimulation::step", rc);
 }
 template <int D>
 void HipSimulation<D>::step_kdk(double dt, int nsteps) {
-    const int rc = nbx_node_step_kdk(node_, G_, dt, nsteps);
+    int rc = NBX_OK;
+    if (ctx_) {
+        if (nsteps < 0) rc = NBX_ERR_INVALID;
+        if (!rc && nsteps > 0) {
+            rc = nbx_ctx_compute_accel(ctx_, NBX_SRC_ALL);
+            for (int s = 0; s < nsteps && !rc; ++s) {
+                rc = nbx_ctx_kick_drift2(ctx_, G_, s == 0 ? 0.5 * dt : dt, dt);
+                if (!rc) rc = nbx_ctx_compute_accel(ctx_, NBX_SRC_ALL);
+            }
+            if (!rc) rc = nbx_ctx_kick_drift2(ctx_, G_, 0.5 * dt, 0.0);
+        }
+    } else {
+        rc = nbx_node_step_kdk(node_, G_, dt, nsteps);
+    }
     if (rc != NBX_OK) raise("HipSimulation::step_kdk", rc);
 }
 template <int D>
+nbx_step_clock HipSimulation<D>::step_kdk_adaptive(const nbx_step_control& control, int max_steps) {
+    if (!ctx_) throw std::runtime_error("HipSimulation::step_kdk_adaptive: the simulation is sharded over several devices; steps chosen on the device need one GPU");
+    nbx_step_clock clock{};
+    int rc = nbx_ctx_step_kdk_adaptive(ctx_, G_, &control, max_steps);
+    if (!rc && max_steps > 0) rc = nbx_ctx_get_step_clock(ctx_, &clock);
+    if (rc != NBX_OK) raise("HipSimulation::step_kdk_adaptive", rc);
+    return clock;
+}
+template <int D>
+double HipSimulation<D>::max_accel() {
+    if (!ctx_) throw std::runtime_error("HipSimulation::max_accel: the simulation is sharded over several devices; the largest acceleration is taken on one GPU");
+    double a = 0.0;
+    int rc = nbx_ctx_max_accel(ctx_, G_, &a);
+    if (rc == NBX_ERR_STATE) {   // no evaluation on the device yet (or the bodies have moved since): make one
+        rc = nbx_ctx_compute_accel(ctx_, NBX_SRC_ALL);
+        if (!rc) rc = nbx_ctx_max_accel(ctx_, G_, &a);
+    }
+    if (rc != NBX_OK) raise("HipSimulation::max_accel", rc);
+    return a;
+}
+template <int D>
+void HipSimulation<D>::step_range(double& dt_smallest, double& dt_largest) {
+    if (!ctx_) throw std::runtime_error("HipSimulation::step_range: the simulation is sharded over several devices; steps chosen on the device need one GPU");
+    dt_smallest = dt_largest = 0.0;
+    std::size_t count = 0;
+    int rc = nbx_ctx_get_step_history(ctx_, nullptr, nullptr, 0, &count);
+    std::vector<double> dts(count);
+    if (!rc && count) rc = nbx_ctx_get_step_history(ctx_, nullptr, dts.data(), count, &count);
+    if (rc != NBX_OK) raise("HipSimulation::step_range", rc);
+    for (double dt : dts) {   // the closing evaluation's entry has dt = 0: no step
+        if (!(dt > 0.0)) continue;
+        dt_smallest = dt_smallest > 0.0 ? std::min(dt_smallest, dt) : dt;
+        dt_largest = std::max(dt_largest, dt);
+    }
+}
+template <int D>
 void HipSimulation<D>::energy(double& kinetic, double& potential) {
-    const int rc = nbx_node_energy(node_, G_, &kinetic, &potential);
+    const int rc = ctx_ ? nbx_ctx_energy(ctx_, G_, &kinetic, &potential) : nbx_node_energy(node_, G_, &kinetic, &potential);
     if (rc != NBX_OK) raise("HipSimulation::energy", rc);
 }
 template <int D>
 void HipSimulation<D>::download(std::vector<Body<D>>& bodies) {
-    int rc = nbx_node_synchronize(node_);
-    if (!rc) rc = nbx_node_download_bodies(node_, bodies.data(), sizeof(Body<D>));
+    int rc = ctx_ ? nbx_ctx_synchronize(ctx_) : nbx_node_synchronize(node_);
+    if (!rc) rc = ctx_ ? nbx_ctx_download_bodies(ctx_, bodies.data(), sizeof(Body<D>)) : nbx_node_download_bodies(node_, bodies.data(), sizeof(Body<D>));
     if (rc != NBX_OK) raise("HipSimulation::download", rc);
 }
 template <int D>
 double HipSimulation<D>::force_kernel_seconds() {
     float mean = 0.f;
     int launches = 0;
-    const int rc = nbx_node_kernel_time(node_, &mean, &launches);
+    const int rc = ctx_ ? nbx_ctx_kernel_time(ctx_, &mean, &launches) : nbx_node_kernel_time(node_, &mean, &launches);
     if (rc != NBX_OK) raise("HipSimulation::force_kernel_seconds", rc);
     return (double)mean * launches / ranks_ * 1e-3;
 }

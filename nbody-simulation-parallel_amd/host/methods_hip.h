@@ -10,6 +10,8 @@
 
 #include <vector>
 
+#include "nbody_hip.h"  // nbx_step_control / nbx_step_clock of HipSimulation::step_kdk_adaptive
+
 #if __has_include("nbody_types.h")
 #include "nbody_types.h"  // this repository's layout-locked Vector<D> / Body<D>
 #else
@@ -67,11 +69,19 @@ public:
     HipSimulation& operator=(const HipSimulation&) = delete;
     void step(double dt, int nsteps);            // asynchronous; the reference helpers' order: kick, then drift
     void step_kdk(double dt, int nsteps);        // extension: synchronised kick-drift-kick leapfrog (second order)
+    // extension: kick-drift-kick with every step chosen on the device (nbx_ctx_step_kdk_adaptive): at most max_steps steps under
+    // `control`; returns the device's clock (which synchronises).  max_accel: the largest |acceleration| of the evaluation on the
+    // device, computing one first when there is none (nbx_ctx_max_accel).  One GPU only: on a simulation sharded over several
+    // devices (set_hip_devices) both throw std::runtime_error -- the sharded loop needs an all-reduce of the maximum.
+    nbx_step_clock step_kdk_adaptive(const nbx_step_control& control, int max_steps);
+    double max_accel();
+    void step_range(double& dt_smallest, double& dt_largest);   // over the steps of the last step_kdk_adaptive call (0, 0: it took none)
     void energy(double& kinetic, double& potential);  // of the whole system, under the reference law's potential
     void download(std::vector<Body<D>>& bodies);
     double force_kernel_seconds();               // per-rank force-kernel time since the last call
 private:
-    struct nbx_node* node_ = nullptr;
+    struct nbx_node* node_ = nullptr;            // several devices: one rank per device ...
+    struct nbx_ctx* ctx_ = nullptr;              // ... one device: the context itself, driven with the calls a one-rank node makes
     double G_;
     int ranks_ = 1;
 };

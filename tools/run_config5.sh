@@ -20,6 +20,8 @@
 #   METHOD=tree INTEGRATOR=kdka ACCEL_LENGTH=1.5 LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # ... with every step chosen
 #                                              # on the device (nbx_leaf_plan_step_kdk_adaptive): dt = sqrt(ACCEL_LENGTH / a_max) up to 0.5,
 #                                              # STEPS the cap; DT_MIN, T_END and POW2=1 as nbody_sim's --dt-min, --t-end, --pow2; rows with `_kdka`
+#   INTEGRATOR=kdka ACCEL_LENGTH=1.5 LAW=newton SOFTENING=600 G=0.1 GPUS=1 tools/run_config5.sh   # the all-pairs loop with every step chosen
+#                                              # on the device (nbx_ctx_step_kdk_adaptive), one GPU only: row Leapfrog_HIP_<steps>steps_kdka
 #   STEPS=250 DUMP=seg1 tools/run_config5.sh
 #   STEPS=250 LOAD=seg1_Leapfrog_HIP.f64 STEP_OFFSET=250 E0=<E of step 0> DUMP=seg2 tools/run_config5.sh   ... and so on;
 # k + k steps through a dump/load equal 2k steps bit for bit (tests/test_gpu_harness.py).  The state file is 56 B per body
@@ -35,7 +37,7 @@ G="${G:-0.05}"
 SOFTENING="${SOFTENING:-0}"
 LAW="${LAW:-reference}"
 METHOD="${METHOD:-brute}"            # brute = the all-pairs loop (-m g); tree = the adaptive octree on one GPU (-m t --leaf-cap 32 --far-order 1)
-INTEGRATOR="${INTEGRATOR:-kd}"       # kd = the reference helpers' order (kick, drift); kdk = synchronised leapfrog (extension); kdka (METHOD=tree) = kdk, steps chosen on the device
+INTEGRATOR="${INTEGRATOR:-kd}"       # kd = the reference helpers' order (kick, drift); kdk = synchronised leapfrog (extension); kdka (METHOD=tree, or METHOD=brute with GPUS=1) = kdk, steps chosen on the device
 ACCEL_LENGTH="${ACCEL_LENGTH:-}"; DT_MIN="${DT_MIN:-}"; T_END="${T_END:-}"; POW2="${POW2:-0}"   # INTEGRATOR=kdka's control
 ENERGY="${ENERGY:-allpairs}"         # with METHOD=tree: tree = also log the energy through the tree itself (--energy-tree)
 LOAD="${LOAD:-}"; STEP_OFFSET="${STEP_OFFSET:-0}"; E0="${E0:-}"; DUMP="${DUMP:-}"
@@ -49,8 +51,11 @@ if [ -n "$DEVICES" ]; then where=(--devices "$DEVICES"); else where=(--gpus "$GP
 if [ "$ENERGY" != allpairs ] && [ "$ENERGY" != tree ]; then
     echo "ENERGY must be allpairs or tree" >&2; exit 1
 fi
-if [ "$INTEGRATOR" = kdka ] && { [ "$METHOD" != tree ] || [ -z "$ACCEL_LENGTH" ]; }; then
-    echo "INTEGRATOR=kdka needs METHOD=tree and ACCEL_LENGTH" >&2; exit 1
+if [ "$INTEGRATOR" = kdka ] && [ -z "$ACCEL_LENGTH" ]; then
+    echo "INTEGRATOR=kdka needs ACCEL_LENGTH" >&2; exit 1
+fi
+if [ "$INTEGRATOR" = kdka ] && [ "$METHOD" = brute ] && { [ "$GPUS" != 1 ] || [ -n "$DEVICES" ]; }; then
+    echo "INTEGRATOR=kdka METHOD=brute needs GPUS=1 and no DEVICES: the all-pairs loop chooses its steps on ONE device" >&2; exit 1
 fi
 if [ "$METHOD" = tree ]; then
     energy=()
@@ -68,6 +73,12 @@ if [ "$METHOD" = tree ]; then
 elif [ "$METHOD" != brute ]; then
     echo "METHOD must be brute or tree" >&2; exit 1
 fi
+if [ "$INTEGRATOR" = kdka ]; then
+    where+=(--accel-length "$ACCEL_LENGTH")
+    [ -n "$DT_MIN" ] && where+=(--dt-min "$DT_MIN")
+    [ -n "$T_END" ] && where+=(--t-end "$T_END")
+    [ "$POW2" = 1 ] && where+=(--pow2)
+fi
 ./nbody_sim -N "$N" -d 3 -m g --init plummer --seed 5 --G "$G" --law "$LAW" --integrator "$INTEGRATOR" --softening "$SOFTENING" --dt 0.5 --steps "$STEPS" --energy-every "$EVERY" "${where[@]}" | tee "$OUT"
-grep -E "^step |Time taken|Kernel time" "$OUT" > "${OUT%.log}.summary.txt"
+grep -E "^step |Time taken|Kernel time|^Adaptive steps" "$OUT" > "${OUT%.log}.summary.txt"
 echo "summary: ${OUT%.log}.summary.txt"
