@@ -22,7 +22,7 @@ all: lib oracle nbody_sim
 lib: $(LIB)
 
 OBJS := $(addprefix $(CSRC)/,$(addsuffix $(O),force_kernel force_sym_kernel force_launch state_kernels nbx_api nbx_node leaf_pair_kernel \
-          leaf_plan_api leaf_far_kernel leaf_phi_kernel octree_device close_hash measure_kernels))
+          leaf_plan_api leaf_far_kernel leaf_phi_kernel octree_device close_hash measure_kernels active_kernel))
 # name of the force-kernel variant used when the caller does not pick one
 # (round 4: the three-level summation build -- same pair arithmetic, fp32 errors ~3x smaller for +1.5 % time)
 DEFAULT_VARIANT ?= fastpk3l_t8_w3_u4
@@ -44,8 +44,12 @@ $(CSRC)/force_launch$(O): $(CSRC)/force_launch.hip $(CSRC)/nbx_internal.h $(CSRC
 	$(HIPCC) $(HIPFLAGS) -DNBX_DEFAULT_VARIANT='"$(DEFAULT_VARIANT)"' -DNBX_DEFAULT_EXACT_VARIANT='"$(DEFAULT_EXACT_VARIANT)"' -c $< -o $@
 
 # -ffp-contract=off: the fp64 kick/drift must round like the reference's two-step arithmetic
-$(CSRC)/state_kernels$(O): $(CSRC)/state_kernels.hip $(CSRC)/nbx_internal.h
+$(CSRC)/state_kernels$(O): $(CSRC)/state_kernels.hip $(CSRC)/nbx_internal.h $(CSRC)/device_sort.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
+
+# forces on a device-resident list of targets: the force kernels' flags
+$(CSRC)/active_kernel$(O): $(CSRC)/active_kernel.hip $(CSRC)/nbx_internal.h
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/nbx_api$(O): $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h $(CSRC)/device_block.h include/nbody_hip.h Makefile
 	$(HIPCC) $(HIPFLAGS) -DNBX_SYM_DEFAULT=$(SYM_DEFAULT) -c $< -o $@

@@ -554,6 +554,85 @@ int nbx_ctx_step_kdk_adaptive(nbx_ctx* ctx, double G, const nbx_step_control* co
 int nbx_ctx_get_step_clock(nbx_ctx* ctx, nbx_step_clock* clock);
 int nbx_ctx_get_step_history(nbx_ctx* ctx, double* a_max_out, double* dt_out, size_t capacity, size_t* count);
 
+/* EXTENSION: forces on a list of targets.  Single-shard contexts with a softening length > 0, under either law.
+ * nbx_ctx_compute_accel_active: for every r < n_targets the sum over ALL n_total bodies, at the positions the context holds now, of
+ * the law's pair term on body targets[r] -- what nbx_ctx_compute_accel computes for that body, in the same fp32 pair arithmetic
+ * (a tile of 256 sources summed in fp32, the tiles in fp64), for O(n_targets * n_total) work.  The list may be in any order and may
+ * repeat an index: each row is evaluated by itself.  n_targets == 0 is legal.  The list is copied to the device (the call returns
+ * when the copy has; the kernels run asynchronously); on the device the list's LENGTH is a word in memory too, and everything about
+ * the launch that depends on it is decided there -- the block-step loop below fills list and length without the host.  Two builds
+ * are queued, one target per lane for a short list and eight for a long one; each returns at once unless the length is on its side
+ * of a threshold (NBODY_HIP_ACTIVE_LONG_LIST in [1, 2^31], read when the context is created, overrides the library's).  The two
+ * agree to rounding, not bit for bit; the same build of the same list gives the same bits (no floating-point atomics).
+ * An OBSERVER: the context's accelerations (nbx_ctx_get_forces, _kick_drift), bodies and step clocks are untouched.
+ * nbx_ctx_get_forces_active: row r of forces_out (n_targets x Vector<dim>, list order) = the force on body targets[r], with
+ * nbx_ctx_get_forces' sign and G m_i scaling.  Synchronises the stream.
+ * Refusals, before anything is launched.  NBX_ERR_INVALID (these need no device): a null context; a null list with n_targets > 0;
+ * an index >= n_total; a null forces_out with rows to write.  NBX_ERR_STATE: nothing uploaded; n_shards != 1; softening 0;
+ * nbx_ctx_get_forces_active without a preceding nbx_ctx_compute_accel_active (an upload or a block-step call ends its validity).
+ * The m / eps^p range rule of nbx_ctx_compute_accel applies (NBX_ERR_INVALID). */
+int nbx_ctx_compute_accel_active(nbx_ctx* ctx, const uint32_t* targets, size_t n_targets);
+int nbx_ctx_get_forces_active(nbx_ctx* ctx, double G, double* forces_out);
+
+/* EXTENSION: kick-drift-kick with BLOCK time steps.  Body i has its own step dt_max 2^-level_i; every body drifts on the smallest step
+ * present (O(N)); forces are computed, through nbx_ctx_compute_accel_active's kernels, only for the bodies whose own step ends
+ * (O(n_active N)).  Lists, levels, the clock and every decision stay on the device.  The rule, in fp64 without contraction:
+ *       tick = dt_max 2^-L;  level l has the step dt_l = dt_max 2^-l = 2^(L-l) ticks;  T_end = n_blocks 2^L
+ *       want(a): raw = sqrt(accel_length / a), +infinity when a == 0;  w = 0; d = dt_max; while (d > raw && w < L) { d = 0.5 d; ++w; }
+ *       T = 0; all bodies active
+ *       for every evaluation:
+ *           sums of the active bodies (ascending body index) from ALL bodies' current positions;  a_i = |G| |A_i|
+ *           any a_i not finite: status = 1; stop                                  (nobody is kicked with these sums)
+ *           for active i, old = level_i, w = want(a_i):
+ *               first evaluation of the call:  new = w;  kick = 0.5 dt_new
+ *               later:  new = w        if w > old
+ *                       new = old - 1  if w < old and old > 0 and T % 2^(L-old+1) == 0        (one level up, where the longer step is aligned)
+ *                       new = old      otherwise;   at T == T_end: new = old
+ *                       kick = 0.5 dt_old + (T == T_end ? 0 : 0.5 dt_new)
+ *               v_i += (F_i / m_i) kick                                           (nbx_ctx_kick_drift2's arithmetic and sign)
+ *               level_i = new
+ *           record (n_active, dn);  pair_terms += n_active n_total                 (dn: the ticks of the drift that follows, 0 when none does)
+ *           T == T_end: finished = 1; stop
+ *           substeps == max_substeps: status = 2; stop
+ *           dn = 2^(L - deepest level present among ALL bodies)
+ *           x += v (dn tick) for ALL bodies, the fp32 positions refreshed;  T += dn;  t = t_start + T tick;  substeps += 1
+ *           active = { i : T % 2^(L - level_i) == 0 }
+ * T is always a multiple of every present step, so every body is active at T_end and afterwards x and v are at one time.  levels = 0
+ * is nbx_ctx_step_kdk(dt_max, n_blocks) through the list kernels.  A later call starts from fresh levels.
+ * TIME LEVELS: after status == 2 (max_substeps reached before T_end) the bodies are NOT at one time: x is at t, body i's velocity is
+ * half its own step behind the end of its last step, and a later call does not resume this one.  After status == 1 the loop stopped
+ * before the kick of the evaluation whose sums were not finite.  Afterwards the context holds no valid accelerations.
+ * The call is asynchronous and reads nothing back to choose anything: it queues evaluations up to number max_substeps + 1; behind the
+ * stop every kernel returns at once.  (It stops queueing early once a 4-byte look it makes anyway has shown the stop --
+ * NBODY_HIP_STEP_WINDOW, as for nbx_ctx_step_kdk_adaptive; the results do not depend on it.)
+ * Refusals, before anything is launched.  NBX_ERR_INVALID (all of these need no device): a null control, a field outside the range
+ * given with it, reserved != 0, n_blocks < 0, max_substeps < 0 or > 1 << 20; a null context.  NBX_ERR_STATE: nothing uploaded, a
+ * context with n_shards != 1, softening 0.  n_blocks == 0 does nothing and leaves no clock.
+ * nbx_ctx_get_block_clock: where the last block-step call left the device's clock; synchronises.  deepest_level is the deepest level
+ * any body held during the call.  nbx_ctx_get_block_history: the (n_active, dn) pairs recorded, oldest first: *count is how many there
+ * are, min(capacity, *count) are written (either array may be null).  nbx_ctx_get_block_levels: the bodies' levels as the call left
+ * them (count entries).  All three: NBX_ERR_STATE before the first block-step call. */
+typedef struct nbx_block_control {
+    double accel_length;   /* c > 0, finite */
+    double dt_max;         /* > 0, finite */
+    double t_start;        /* finite */
+    int    levels;         /* L in [0, 20] */
+    int    reserved;       /* must be 0 */
+} nbx_block_control;
+typedef struct nbx_block_clock {
+    double t;
+    uint64_t ticks;        /* T */
+    uint64_t pair_terms;   /* sum over the evaluations of n_active * n_total */
+    uint32_t substeps, evaluations;
+    int deepest_level;
+    int finished;          /* 1: T reached T_end */
+    int status;            /* 0 ok; 1: an acceleration was not finite; 2: max_substeps reached before the end */
+} nbx_block_clock;
+int nbx_ctx_step_kdk_block(nbx_ctx* ctx, double G, const nbx_block_control* control, int n_blocks, int max_substeps);
+int nbx_ctx_get_block_clock(nbx_ctx* ctx, nbx_block_clock* clock);
+int nbx_ctx_get_block_history(nbx_ctx* ctx, uint32_t* n_active_out, uint32_t* ticks_out, size_t capacity, size_t* count);
+int nbx_ctx_get_block_levels(nbx_ctx* ctx, int32_t* levels_out);
+
 /* Forces of this shard's targets as Vector<dim>[count] doubles: F_i = -(G m_i) a_i.  count = this shard's bodies: shard_len, or
  * fewer -- possibly none -- for the last shards (a shard g with g * shard_len >= n_total is empty); exactly count rows are written.
  * Synchronises the stream. */

@@ -91,6 +91,12 @@ ABI = [
     ("nbx_ctx_step_kdk_adaptive", _i, [_vp, _d, _vp, _i]),
     ("nbx_ctx_get_step_clock", _i, [_vp, _vp]),
     ("nbx_ctx_get_step_history", _i, [_vp, _vp, _vp, _sz, _c.POINTER(_sz)]),
+    ("nbx_ctx_compute_accel_active", _i, [_vp, _vp, _sz]),
+    ("nbx_ctx_get_forces_active", _i, [_vp, _d, _vp]),
+    ("nbx_ctx_step_kdk_block", _i, [_vp, _d, _vp, _i, _i]),
+    ("nbx_ctx_get_block_clock", _i, [_vp, _vp]),
+    ("nbx_ctx_get_block_history", _i, [_vp, _vp, _vp, _sz, _c.POINTER(_sz)]),
+    ("nbx_ctx_get_block_levels", _i, [_vp, _vp]),
     ("nbx_ctx_get_forces", _i, [_vp, _d, _vp]),
     ("nbx_ctx_accuracy", _i, [_vp, _d, _vp, _pd]),
     ("nbx_ctx_get_accel", _i, [_vp, _vp]),
@@ -238,6 +244,21 @@ class StepClock(ctypes.Structure):
     def __repr__(self):
         return (f"StepClock(t={self.t!r}, dt_last={self.dt_last!r}, a_max_last={self.a_max_last!r}, steps={self.steps}, "
                 f"evaluations={self.evaluations}, finished={self.finished}, status={self.status})")
+
+
+class BlockControl(ctypes.Structure):
+    """nbx_block_control of include/nbody_hip.h: how nbx_ctx_step_kdk_block chooses its levels."""
+    _fields_ = [("accel_length", _d), ("dt_max", _d), ("t_start", _d), ("levels", _i), ("reserved", _i)]
+
+
+class BlockClock(ctypes.Structure):
+    """nbx_block_clock of include/nbody_hip.h: where a block-step call left the device's clock."""
+    _fields_ = [("t", _d), ("ticks", _c.c_uint64), ("pair_terms", _c.c_uint64), ("substeps", _c.c_uint32), ("evaluations", _c.c_uint32),
+                ("deepest_level", _i), ("finished", _i), ("status", _i)]
+
+    def __repr__(self):
+        return (f"BlockClock(t={self.t!r}, ticks={self.ticks}, pair_terms={self.pair_terms}, substeps={self.substeps}, "
+                f"evaluations={self.evaluations}, deepest_level={self.deepest_level}, finished={self.finished}, status={self.status})")
 
 
 def set_default_refine(rel_tolerance: float, sigma_factor: float = 0.0):
@@ -724,6 +745,51 @@ class Context:
             self._ck(self.lib.nbx_ctx_get_step_history(self.h, a.ctypes.data, dt.ctypes.data, count.value, ctypes.byref(count)),
                      "nbx_ctx_get_step_history")
         return a, dt
+
+    def compute_accel_active(self, targets):
+        """The sums of the listed bodies against all bodies (nbx_ctx_compute_accel_active): any order, repeats allowed, an observer of the
+        context.  Single shard, softening > 0."""
+        t = np.ascontiguousarray(targets, dtype=np.uint32).reshape(-1)
+        self._ck(self.lib.nbx_ctx_compute_accel_active(self.h, t.ctypes.data if t.size else None, t.size), "nbx_ctx_compute_accel_active")
+        self._active_rows = int(t.size)
+
+    def forces_active(self, G: float = REFERENCE_G) -> np.ndarray:
+        """[n_targets, dim] forces of the last compute_accel_active, in list order (nbx_ctx_get_forces_active)."""
+        out = np.empty((getattr(self, "_active_rows", 0), self.dim), dtype=np.float64)
+        self._ck(self.lib.nbx_ctx_get_forces_active(self.h, float(G), out.ctypes.data), "nbx_ctx_get_forces_active")
+        return out
+
+    def step_kdk_block(self, accel_length: float, dt_max: float, levels: int, n_blocks: int = 1, max_substeps: int = 1 << 20, t_start: float = 0.0,
+                       G: float = REFERENCE_G) -> "BlockClock":
+        """Kick-drift-kick over n_blocks steps of dt_max with block time steps: body i steps by dt_max / 2^level_i, its level chosen on
+        the device from its own acceleration, and only the bodies whose step ends are evaluated (nbx_ctx_step_kdk_block).  Returns the
+        clock (which synchronises)."""
+        k = BlockControl(float(accel_length), float(dt_max), float(t_start), int(levels), 0)
+        self._ck(self.lib.nbx_ctx_step_kdk_block(self.h, float(G), ctypes.byref(k), int(n_blocks), int(max_substeps)), "nbx_ctx_step_kdk_block")
+        return self.block_clock() if int(n_blocks) > 0 else None
+
+    def block_clock(self) -> "BlockClock":
+        """The device's clock as the last block-step call left it (nbx_ctx_get_block_clock); synchronises."""
+        k = BlockClock()
+        self._ck(self.lib.nbx_ctx_get_block_clock(self.h, ctypes.byref(k)), "nbx_ctx_get_block_clock")
+        return k
+
+    def block_history(self):
+        """(n_active[k], dn[k]) of the evaluations the last block-step call recorded, oldest first; dn in ticks, 0 for the entry no drift
+        followed (nbx_ctx_get_block_history)."""
+        count = ctypes.c_size_t(0)
+        self._ck(self.lib.nbx_ctx_get_block_history(self.h, None, None, 0, ctypes.byref(count)), "nbx_ctx_get_block_history")
+        n, dn = np.zeros(count.value, dtype=np.uint32), np.zeros(count.value, dtype=np.uint32)
+        if count.value:
+            self._ck(self.lib.nbx_ctx_get_block_history(self.h, n.ctypes.data, dn.ctypes.data, count.value, ctypes.byref(count)),
+                     "nbx_ctx_get_block_history")
+        return n, dn
+
+    def block_levels(self) -> np.ndarray:
+        """The bodies' levels as the last block-step call left them (nbx_ctx_get_block_levels)."""
+        out = np.zeros(self.count, dtype=np.int32)
+        self._ck(self.lib.nbx_ctx_get_block_levels(self.h, out.ctypes.data if self.count else None), "nbx_ctx_get_block_levels")
+        return out
 
     def forces(self, G: float = REFERENCE_G) -> np.ndarray:
         out = np.empty((self.count, self.dim), dtype=np.float64)

@@ -163,6 +163,9 @@ constexpr int kPhiSlices = 16;
 // nbx_ctx_step_kdk_adaptive queues at most this many evaluations ahead of its looks at the clock's `stopped`, so at most this many
 // less one are wasted behind the stop (DESIGN.md section 3 has the measurement; NBODY_HIP_STEP_WINDOW in [1, kStepWindowMax] overrides)
 constexpr int kStepWindowDefault = 2;
+// lists of at least this many targets run the long-list build of active_kernel.hip (NBODY_HIP_ACTIVE_LONG_LIST in
+// [1, 2^31] overrides)
+constexpr unsigned kActiveLongListDefault = 2048;
 constexpr int kGraphMinSteps = 4;   // nbx_ctx_step replays a captured step from this many steps on
 // Mixed mode: selection rule |a|^2 < (sigma u / tol)^2 Q (force_kernel.hip).  The sigma factor is a calibration of the DEFAULT
 // kernel's summation (round 4: the three-level kernel, whose rounding errors are ~3x smaller than the two-level kernel's at the same
@@ -530,6 +533,7 @@ int upload_finish(nbx_ctx* c, const unsigned long long facts[3]) {
     }
     c->uploaded = true;
     c->have_accel = false;
+    c->have_active = false;
     c->tgt_cand_valid = 0; c->bad_list_pass = -1;
     c->probe_bad = 0;
     c->counters_pending = false; c->steps_since_poll = 0; c->last_cand = c->last_bad = 0;
@@ -672,6 +676,13 @@ int nbx_ctx_create(nbx_ctx** out, int device, int dim, size_t n_total, int n_sha
         const long w = e && *e ? std::strtol(e, &end, 10) : 0;
         if (end && *end == '\0' && w >= 1 && w <= kStepWindowMax) c->step_window = (int)w;
     }
+    {
+        c->active_long_list = kActiveLongListDefault;
+        const char* e = std::getenv("NBODY_HIP_ACTIVE_LONG_LIST");
+        char* end = nullptr;
+        const long long w = e && *e ? std::strtoll(e, &end, 10) : 0;
+        if (end && *end == '\0' && w >= 1 && w <= (1ll << 31)) c->active_long_list = (unsigned)w;
+    }
 #define CTX_TRY(expr)                                                            \
     do {                                                                         \
         hipError_t e_ = (expr);                                                  \
@@ -733,6 +744,9 @@ int nbx_ctx_destroy(nbx_ctx* c) {
     }
     if (c->clock_block) (void)hipFree(c->clock_block);
     if (c->amax_word) (void)hipFree(c->amax_word);
+    for (void* p : {(void*)c->active_list, (void*)c->active_count, (void*)c->active_part, (void*)c->active_sums, (void*)c->block_clock,
+                    (void*)c->block_level, (void*)c->block_flags, (void*)c->block_tile_sums})
+        if (p) (void)hipFree(p);
     if (c->stop_ring) (void)hipHostFree(c->stop_ring);
     for (auto e : c->stop_ev) if (e) (void)hipEventDestroy(e);
     if (c->counters_host) (void)hipHostFree(c->counters_host);
@@ -1184,6 +1198,13 @@ int nbx_ctx_max_accel(nbx_ctx* c, double G, double* a_max) {
     return NBX_OK;
 }
 
+// what the stepping loops' looks at `stopped` need
+static int ctx_fit_stop_ring(nbx_ctx* c) {
+    if (!c->stop_ring) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->stop_ring), kStepWindowMax * sizeof(int), hipHostMallocDefault));
+    if (c->stop_ev.empty()) c->stop_ev.assign(kStepWindowMax, nullptr);
+    return NBX_OK;
+}
+
 // The step clock's block with room for a call of max_steps steps, and what the loop's looks need.  Growing the block waits for
 // the context's queued work first: an earlier call's kernels may still read the one held.
 static int ctx_fit_clock(nbx_ctx* c, int max_steps) {
@@ -1198,9 +1219,7 @@ static int ctx_fit_clock(nbx_ctx* c, int max_steps) {
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->clock_block), need));
         c->clock_bytes = need;
     }
-    if (!c->stop_ring) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->stop_ring), kStepWindowMax * sizeof(int), hipHostMallocDefault));
-    if (c->stop_ev.empty()) c->stop_ev.assign(kStepWindowMax, nullptr);
-    return NBX_OK;
+    return ctx_fit_stop_ring(c);
 }
 
 // nbx_ctx_step_kdk with every kick read from the clock.  Per evaluation e = 0 .. max_steps the stream gets: the force launch (and
@@ -1296,6 +1315,222 @@ int nbx_ctx_get_step_history(nbx_ctx* c, double* a_max_out, double* dt_out, size
             if (dt_out) dt_out[i] = pairs[2 * i + 1];
         }
     }
+    return NBX_OK;
+}
+
+// ---- forces on a list of targets; kick-drift-kick with block time steps (include/nbody_hip.h has the rule) ----
+// Room for a list of `cap` targets: the list, the fp64 slice sums and the folded sums.  The slice sums hold every target in 8 to 64
+// slices (more for a small shard: 2^21 rows in all, where the buffer stays at 50 MB per component plane) and a list of up to 4,096
+// targets in all 256; active_layout picks slices x stride within that on the device.  Growing waits for the queued work first.
+static int ctx_fit_active(nbx_ctx* c, size_t want_cap) {
+    if (want_cap < c->count) want_cap = c->count;
+    if (want_cap < 1) want_cap = 1;
+    if (c->active_list && c->active_cap >= want_cap) return NBX_OK;
+    if (c->active_list) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (void** p : {(void**)&c->active_list, (void**)&c->active_part, (void**)&c->active_sums}) { HIP_TRY(hipFree(*p)); *p = nullptr; }
+        c->active_cap = 0;
+    }
+    c->have_active = false;
+    const unsigned long long cap_r = ((unsigned long long)want_cap + 255ull) / 256ull * 256ull;
+    const unsigned long long max_slices = c->pad / kTile < 256u ? c->pad / kTile : 256u;
+    unsigned long long whole = (1ull << 21) / cap_r;
+    whole = whole < 8 ? 8 : whole > 64 ? 64 : whole;
+    if (whole > max_slices) whole = max_slices;
+    const unsigned long long per_comp = std::max(cap_r * whole, std::min(cap_r, 4096ull) * max_slices);
+    c->active_budget = (unsigned long long)c->dim * per_comp;
+    if (!c->active_count) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->active_count), 256));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->active_list), want_cap * sizeof(unsigned)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->active_part), c->active_budget * sizeof(double)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->active_sums), (size_t)c->dim * want_cap * sizeof(double)));
+    c->active_cap = (unsigned)want_cap;
+    return NBX_OK;
+}
+
+static ActiveArgs active_args(const nbx_ctx* c, const unsigned* count, const int* stopped) {
+    ActiveArgs a = {};
+    a.pos_all = c->pos_all; a.mass_all = c->mass_all; a.list = c->active_list; a.count = count;
+    a.part = c->active_part; a.sums = c->active_sums; a.stopped = stopped; a.budget = c->active_budget;
+    a.pad = c->pad; a.cap = c->active_cap; a.long_list = c->active_long_list;
+    a.max_slices = c->pad / kTile < 256u ? (int)(c->pad / kTile) : 256;
+    a.dim = c->dim; a.law = c->law; a.eps2 = (float)(c->softening * c->softening);
+    return a;
+}
+
+// what both new capabilities ask of the context (after the arguments have been judged)
+static int active_state_refusal(const nbx_ctx* c, const char* who) {
+    static thread_local std::string msg;
+    if (!c->uploaded) return fail(NBX_ERR_STATE, "upload bodies first");
+    if (c->n_shards != 1) { msg = std::string(who) + " drives single-shard contexts only"; return fail(NBX_ERR_STATE, msg.c_str()); }
+    if (!(c->softening > 0.0)) { msg = std::string(who) + " needs a softening length (nbx_ctx_set_softening)"; return fail(NBX_ERR_STATE, msg.c_str()); }
+    return law_refusal(c);
+}
+
+int nbx_ctx_compute_accel_active(nbx_ctx* c, const uint32_t* targets, size_t n_targets) {
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    if (!targets && n_targets) return fail(NBX_ERR_INVALID, "null argument");
+    if (n_targets > ((size_t)1 << 31)) return fail(NBX_ERR_INVALID, "n_targets too large");
+    for (size_t r = 0; r < n_targets; ++r)
+        if (targets[r] >= c->n_total) return fail(NBX_ERR_INVALID, "a target index is >= n_total");
+    int rc = active_state_refusal(c, "nbx_ctx_compute_accel_active");
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ctx_fit_active(c, n_targets))) return rc;
+    const unsigned n32 = (unsigned)n_targets;
+    if (n_targets) HIP_TRY(hipMemcpyAsync(c->active_list, targets, n_targets * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->active_count, &n32, sizeof n32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's list is borrowed only for this call; the kernels below run asynchronously
+    HIP_TRY(launch_active_accel(active_args(c, c->active_count, nullptr), c->stream));
+    c->active_n = n_targets;
+    c->have_active = true;
+    return NBX_OK;
+}
+
+int nbx_ctx_get_forces_active(nbx_ctx* c, double G, double* out) {
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    if (!c->have_active) return fail(NBX_ERR_STATE, "no forces of a target list on the device (nbx_ctx_compute_accel_active)");
+    if (!out && c->active_n) return fail(NBX_ERR_INVALID, "null argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t bytes = c->active_n * c->dim * sizeof(double);
+    if ((rc = ensure_stage(c, bytes ? bytes : 8))) return rc;
+    HIP_TRY(launch_active_export(active_args(c, c->active_count, nullptr), c->law ? -G : G, c->m64, c->stage, c->stream));
+    if (bytes) HIP_TRY(hipMemcpyAsync(out, c->stage, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return NBX_OK;
+}
+
+static const char* block_control_fault(const nbx_block_control* k) {
+    if (!(k->accel_length > 0.0) || !std::isfinite(k->accel_length)) return "accel_length must be finite and > 0";
+    if (!(k->dt_max > 0.0) || !std::isfinite(k->dt_max)) return "dt_max must be finite and > 0";
+    if (!std::isfinite(k->t_start)) return "t_start must be finite";
+    if (k->levels < 0 || k->levels > 20) return "levels must be in [0, 20]";
+    if (k->reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
+static int ctx_fit_block(nbx_ctx* c, int max_substeps) {
+    const size_t need = kBlockClockHistoryOffset + ((size_t)max_substeps + 1) * 2 * sizeof(uint32_t);
+    if (c->block_clock_bytes < need) {
+        if (c->block_clock) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(hipFree(c->block_clock));
+            c->block_clock = nullptr; c->block_clock_bytes = 0;
+        }
+        c->block_valid = false;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->block_clock), need));
+        c->block_clock_bytes = need;
+    }
+    if (!c->block_level) {   // a context's count never changes
+        const size_t n = c->count ? c->count : 1;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->block_level), n * sizeof(int)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->block_flags), (n + 1) * sizeof(unsigned)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->block_tile_sums), ((n + 2047) / 2048 + 1) * sizeof(unsigned)));
+        c->block_cap = n;
+    }
+    return ctx_fit_stop_ring(c);
+}
+
+// Per evaluation e = 0 .. max_substeps the stream gets: both force builds and the fold (each reads the active list's length where the
+// select left it), the check, the controller's first half, the kick of the active bodies, the controller's second half, the drift of
+// all bodies, the select of the next list.  The host reads nothing to choose anything; it looks at `stopped` through
+// nbx_ctx_step_kdk_adaptive's ring and window.
+int nbx_ctx_step_kdk_block(nbx_ctx* c, double G, const nbx_block_control* control, int n_blocks, int max_substeps) {
+    if (!control) return fail(NBX_ERR_INVALID, "null argument");
+    if (const char* why = block_control_fault(control)) return fail(NBX_ERR_INVALID, why);
+    if (n_blocks < 0) return fail(NBX_ERR_INVALID, "n_blocks < 0");
+    if (max_substeps < 0 || max_substeps > (1 << 20)) return fail(NBX_ERR_INVALID, "max_substeps must be in [0, 1 << 20]");
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    int rc = active_state_refusal(c, "nbx_ctx_step_kdk_block");
+    if (rc) return rc;
+    if (n_blocks == 0) return NBX_OK;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ctx_fit_active(c, c->count))) return rc;
+    if ((rc = ctx_fit_block(c, max_substeps))) return rc;
+    hipStream_t s = c->stream;
+    BlockStepArgs b = {};
+    b.clock = reinterpret_cast<BlockClock*>(c->block_clock);
+    b.level = c->block_level; b.list = c->active_list; b.flags = c->block_flags; b.tile_sums = c->block_tile_sums;
+    b.sums = c->active_sums; b.cap = c->active_cap; b.dim = c->dim; b.pad = c->pad; b.count = c->count;
+    b.G = c->law ? -G : G; b.absG = std::fabs(G);
+    b.x64 = c->x64; b.v64 = c->v64; b.m64 = c->m64;
+    b.pos_chunk = c->pos_all + (size_t)c->shard * c->dim * c->pad;
+    HIP_TRY(launch_block_clock_init(b, control->accel_length, control->dt_max, control->t_start, control->levels,
+                                    (unsigned long long)n_blocks << control->levels, (uint32_t)max_substeps, (uint32_t)max_substeps + 1u, s));
+    HIP_TRY(launch_block_select(b, s));   // T = 0, every level 0: all bodies
+    c->block_valid = true;
+    c->have_active = false;               // the list and its sums are the loop's now
+    c->have_accel = false;
+    c->tgt_cand_valid = 0; c->bad_list_pass = -1;
+    const ActiveArgs A = active_args(c, &b.clock->n_active, &b.clock->stopped);
+    // an evaluation behind the stop costs a dozen launches that return at once, not a pass -- and still a larger window only adds them:
+    // W = 2 measured best here too
+    const int W = c->step_window;
+    for (int e = 0; e <= max_substeps; ++e) {
+        if (e >= W) {
+            const int seen = (e - W) % kStepWindowMax;
+            HIP_TRY(hipEventSynchronize(c->stop_ev[seen]));
+            if (c->stop_ring[seen]) break;
+        }
+        HIP_TRY(launch_active_accel(A, s));
+        HIP_TRY(launch_block_kick(b, s));
+        HIP_TRY(launch_block_advance(b, s));
+        const int slot = e % kStepWindowMax;
+        if (!c->stop_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&c->stop_ev[slot], hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(&c->stop_ring[slot], &b.clock->stopped, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(c->stop_ev[slot], s));
+    }
+    return NBX_OK;
+}
+
+static int ctx_read_block_clock(nbx_ctx* c, BlockClock* host) {
+    HIP_TRY(hipMemcpyAsync(host, c->block_clock, sizeof(BlockClock), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return NBX_OK;
+}
+
+int nbx_ctx_get_block_clock(nbx_ctx* c, nbx_block_clock* out) {
+    if (!c || !out) return fail(NBX_ERR_INVALID, "null argument");
+    if (!c->block_valid) return fail(NBX_ERR_STATE, "no block-step call on this context yet (nbx_ctx_step_kdk_block)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    BlockClock k;
+    if ((rc = ctx_read_block_clock(c, &k))) return rc;
+    out->t = k.t; out->ticks = k.T; out->pair_terms = k.pair_terms;
+    out->substeps = k.substeps; out->evaluations = k.evaluations;
+    out->deepest_level = k.deepest; out->finished = k.finished; out->status = k.status;
+    return NBX_OK;
+}
+
+int nbx_ctx_get_block_history(nbx_ctx* c, uint32_t* n_active_out, uint32_t* ticks_out, size_t capacity, size_t* count) {
+    if (!c || !count) return fail(NBX_ERR_INVALID, "null argument");
+    if (!c->block_valid) return fail(NBX_ERR_STATE, "no block-step call on this context yet (nbx_ctx_step_kdk_block)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    BlockClock k;
+    if ((rc = ctx_read_block_clock(c, &k))) return rc;
+    *count = k.recorded;
+    const size_t take = capacity < (size_t)k.recorded ? capacity : (size_t)k.recorded;
+    if (take && (n_active_out || ticks_out)) {
+        std::vector<uint32_t> pairs;
+        try { pairs.resize(2 * take); } catch (...) { return fail(NBX_ERR_ALLOC, "host allocation failed"); }
+        HIP_TRY(hipMemcpyAsync(pairs.data(), c->block_clock + kBlockClockHistoryOffset, 2 * take * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < take; ++i) {
+            if (n_active_out) n_active_out[i] = pairs[2 * i];
+            if (ticks_out) ticks_out[i] = pairs[2 * i + 1];
+        }
+    }
+    return NBX_OK;
+}
+
+int nbx_ctx_get_block_levels(nbx_ctx* c, int32_t* levels_out) {
+    if (!c || (!levels_out && c->count)) return fail(NBX_ERR_INVALID, "null argument");
+    if (!c->block_valid) return fail(NBX_ERR_STATE, "no block-step call on this context yet (nbx_ctx_step_kdk_block)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if (c->count) HIP_TRY(hipMemcpyAsync(levels_out, c->block_level, c->count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return NBX_OK;
 }
 

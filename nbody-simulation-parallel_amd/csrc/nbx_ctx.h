@@ -114,6 +114,24 @@ struct nbx_ctx {
     int* stop_ring = nullptr;        // pinned [kStepWindowMax]: the look behind evaluation e lands in word e % kStepWindowMax ...
     std::vector<hipEvent_t> stop_ev; // ... and this event says that it has
     unsigned long long* amax_word = nullptr;   // nbx_ctx_max_accel's 8-byte word, its own allocation, made when a caller first asks
+    // forces on a list of targets (nbx_ctx_compute_accel_active) and block time steps (nbx_ctx_step_kdk_block; nbx_internal.h: ActiveArgs,
+    // BlockClock): allocations of their own, made by the first call that needs them
+    unsigned* active_list = nullptr;         // [active_cap]
+    unsigned* active_count = nullptr;        // the device word nbx_ctx_compute_accel_active uploads the list's length into
+    double* active_part = nullptr;           // [slices][dim][stride], active_budget doubles
+    double* active_sums = nullptr;           // [dim][active_cap]
+    unsigned active_cap = 0;
+    unsigned long long active_budget = 0;
+    unsigned active_long_list = 0;           // lists from this length on run the long-list build (NBODY_HIP_ACTIVE_LONG_LIST)
+    size_t active_n = 0;                     // targets of the last nbx_ctx_compute_accel_active
+    bool have_active = false;                // ... and its sums are on the device
+    char* block_clock = nullptr;             // the block clock and, kBlockClockHistoryOffset behind it, the history of the last call
+    size_t block_clock_bytes = 0;
+    bool block_valid = false;                // a block-step call has gone through: the block holds its clock, block_level its levels
+    int* block_level = nullptr;              // [block_cap]
+    unsigned* block_flags = nullptr;         // [block_cap + 1]
+    unsigned* block_tile_sums = nullptr;
+    size_t block_cap = 0;
 };
 
 namespace nbx {

@@ -310,6 +310,73 @@ hipError_t launch_step_control(StepClock* clock, bool last, hipStream_t stream);
 // launch_kick_drift with dt_kick and dt_drift read from the clock (k's own are not read); nothing is touched when clock->apply == 0
 hipError_t launch_kick_drift_clock(const KickDriftArgs& k, const StepClock* clock, hipStream_t stream);
 
+// ---- forces on a list of targets (active_kernel.hip; nbx_ctx_compute_accel_active) and block time steps (nbx_ctx_step_kdk_block) ----
+// One evaluation of the softened laws for the targets list[0 .. *count) against the `pad` entries of chunk 0.  The list and its length
+// live on the device; the launch is sized for `cap` targets and everything that depends on the length -- slices, stride, which of
+// the two instantiations works -- is decided there (active_kernel.hip: active_layout).  part holds [slices][dim][stride] fp64 slice
+// sums, sums the folded [dim][cap] result: row r belongs to list[r].
+struct ActiveArgs {
+    const float* pos_all;        // chunk 0: [dim][pad]
+    const float* mass_all;       // [pad]
+    const unsigned* list;        // [cap]
+    const unsigned* count;       // device word: the list's length (read as min(*count, cap))
+    double* part;                // [slices][dim][stride], at most `budget` doubles
+    double* sums;                // [dim][cap]
+    const int* stopped;          // null, or a device word: non-zero makes every kernel return at once (the block loop's stop)
+    unsigned long long budget;   // doubles in part: >= dim * cap rounded up to 256 (one slice of every target always fits)
+    unsigned pad, cap;
+    unsigned long_list;          // lists of at least this many targets go to the long-list build (8 targets per lane), shorter ones to 1 per lane
+    int max_slices;              // most source slices (<= 256, <= pad / kTile)
+    int dim, law;                // law 0: m d / rho^4, 1: m d / rho^3; rho^2 = r^2 + eps2
+    float eps2;
+};
+constexpr unsigned kActiveLongBlock = 2048;   // targets per workgroup of the long-list build: 256 lanes x 4 float2 pairs
+hipError_t launch_active_accel(const ActiveArgs& a, hipStream_t stream);
+// forces_out: AoS double[*count][dim] on the device, row r = -(G m[list[r]]) sums[.][r]
+hipError_t launch_active_export(const ActiveArgs& a, double G, const double* m64, double* forces_out, hipStream_t stream);
+
+// The device's clock of nbx_ctx_step_kdk_block (include/nbody_hip.h has the rule): this record at the start of one block of device
+// memory, the history -- (n_active, dn) pairs of 32-bit words -- kBlockClockHistoryOffset bytes behind it.
+struct BlockClock {
+    double accel_length, dt_max, tick, t_start, t;
+    double dt_drift;                    // this substep's drift, dn * tick
+    unsigned long long T, T_end, pair_terms, n_total;
+    unsigned n_active;                  // the active list's length: what the force kernels read
+    unsigned n_bodies;                  // = n_total, the select scan's count word
+    unsigned bad;                       // an active body's acceleration was not finite (this evaluation)
+    unsigned pop[21];                   // bodies per level
+    int levels;                         // L
+    int first, closing, apply, drift;   // this evaluation: the call's first / at T_end / kicks are made / a drift follows
+    int stopped, finished, status, deepest;
+    uint32_t substeps, evaluations, recorded, capacity, max_substeps;
+};
+constexpr size_t kBlockClockHistoryOffset = 512;
+static_assert(sizeof(BlockClock) <= kBlockClockHistoryOffset, "the history starts behind the clock");
+struct BlockStepArgs {
+    BlockClock* clock;
+    int* level;                 // [count] the bodies' levels
+    unsigned* list;             // [count] the active list (ascending), its length in clock->n_active
+    unsigned* flags;            // [count + 1] select: 1 for an active body; scanned in place
+    unsigned* tile_sums;        // device_sort.h exclusive_scan's workspace
+    const double* sums;         // [dim][cap] ActiveArgs::sums of this evaluation
+    unsigned cap;
+    int dim;
+    unsigned pad;
+    size_t count;
+    double G;                   // as KickDriftArgs::G (negated for the attractive law)
+    double absG;
+    double* x64; double* v64; const double* m64;
+    float* pos_chunk;
+};
+hipError_t launch_block_clock_init(const BlockStepArgs& b, double accel_length, double dt_max, double t_start, int levels, unsigned long long T_end,
+                                   uint32_t max_substeps, uint32_t capacity, hipStream_t stream);
+// behind an evaluation's fold: the finiteness check, the controller's first half, the kick of the active bodies
+hipError_t launch_block_kick(const BlockStepArgs& b, hipStream_t stream);
+// the controller's second half (history, stop, dn, T), the drift of all bodies, the next active list
+hipError_t launch_block_advance(const BlockStepArgs& b, hipStream_t stream);
+// the active list for the clock's T as it stands (launch_block_advance ends with it; a call starts with it)
+hipError_t launch_block_select(const BlockStepArgs& b, hipStream_t stream);
+
 // forces_out: AoS double[count][dim] on the device
 hipError_t launch_export_forces(const float* acc, int splits, int dim, unsigned pad, size_t count,
                                 double G, const double* m64, double* forces_out, hipStream_t stream);

@@ -5,6 +5,7 @@
 // with exactly the reference's arithmetic (nbody-sim-new/methods.cpp:425-450); only the pair sum
 // feeding it is fp32.  Each drift also refreshes the shard's fp32 chunk of the exchange buffer.
 #include "nbx_internal.h"
+#include "device_sort.h"
 
 namespace nbx {
 namespace {
@@ -318,6 +319,157 @@ __global__ __launch_bounds__(256) void kick_drift_clock_kernel(KickDriftArgs a, 
     a.pos_chunk[(size_t)k * a.pad + l] = (float)x;
 }
 
+// ---- kick-drift-kick with block time steps (nbx_ctx_step_kdk_block; include/nbody_hip.h has the rule) ----
+// Per evaluation the stream carries: the force kernels and their fold (active_kernel.hip), then block_check, block_control_pre,
+// block_kick (launch_block_kick), then block_control_post, block_drift and the select pipeline (launch_block_advance).  The
+// stream orders them: no fence, no ticket.  Once clock->stopped is set every one of them returns at once.
+__global__ void block_clock_init_kernel(BlockClock* __restrict__ c, double accel_length, double dt_max, double t_start, int levels,
+                                        unsigned long long T_end, unsigned long long n_total, uint32_t max_substeps, uint32_t capacity) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    c->accel_length = accel_length; c->dt_max = dt_max; c->t_start = t_start; c->t = t_start;
+    double tick = dt_max;
+    for (int l = 0; l < levels; ++l) tick = 0.5 * tick;     // exact halvings
+    c->tick = tick; c->dt_drift = 0.0;
+    c->T = 0ull; c->T_end = T_end; c->pair_terms = 0ull; c->n_total = n_total;
+    c->n_active = 0u; c->n_bodies = (unsigned)n_total; c->bad = 0u;
+    for (int l = 0; l < 21; ++l) c->pop[l] = 0u;
+    c->levels = levels;
+    c->first = 1; c->closing = 0; c->apply = 0; c->drift = 0;
+    c->stopped = 0; c->finished = 0; c->status = 0; c->deepest = 0;
+    c->substeps = 0u; c->evaluations = 0u; c->recorded = 0u; c->capacity = capacity; c->max_substeps = max_substeps;
+}
+
+__global__ __launch_bounds__(256) void block_levels_init_kernel(int* __restrict__ level, size_t count) {
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l < count) level[l] = 0;
+}
+
+// a_r = absG |A_r| of active row r: what the rule calls a_i (the squares added in component order)
+__device__ __forceinline__ double block_row_accel(const BlockStepArgs& b, unsigned r) {
+    double s2 = 0.0;
+    for (int k = 0; k < b.dim; ++k) { const double s = b.sums[(size_t)k * b.cap + r]; s2 += s * s; }
+    return fabs(b.absG * sqrt(s2));
+}
+
+// "any a_i not finite: status 1, stop; nobody is kicked": the look at every active row comes before the first kick
+__global__ __launch_bounds__(256) void block_check_kernel(BlockStepArgs b) {
+    BlockClock* const c = b.clock;
+    if (c->stopped) return;
+    const unsigned r = blockIdx.x * 256u + threadIdx.x;
+    const bool bad = r < c->n_active && !(block_row_accel(b, r) <= 1.7976931348623157e308);
+    const unsigned long long votes = __ballot(bad);
+    if ((threadIdx.x & 63u) == 0u && votes) atomicOr(&c->bad, 1u);
+}
+
+__global__ void block_control_pre_kernel(BlockClock* __restrict__ c) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    c->apply = 0; c->drift = 0;
+    if (c->stopped) return;
+    c->evaluations += 1u;
+    if (c->bad) { c->status = 1; c->stopped = 1; return; }
+    c->closing = c->T == c->T_end ? 1 : 0;
+    c->apply = 1;
+}
+
+// The active bodies' level rule and kick, one lane per active row (a body's level needs all its components).  The population of
+// the levels is kept with integer atomics: one add per wave and level that gained or lost bodies would be finer, but a substep
+// moves few bodies between levels.
+__global__ __launch_bounds__(256) void block_kick_kernel(BlockStepArgs b) {
+    BlockClock* const c = b.clock;
+    if (c->apply == 0) return;
+    const unsigned r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= c->n_active) return;
+    const unsigned i = b.list[r];
+    const int L = c->levels;
+    const double dt_max = c->dt_max;
+    const unsigned long long T = c->T;
+    const bool first = c->first != 0, closing = c->closing != 0;
+    const double a = block_row_accel(b, r);
+    const double raw = a == 0.0 ? __longlong_as_double(0x7ff0000000000000ll) : sqrt(c->accel_length / a);
+    int w = 0;
+    for (double d = dt_max; d > raw && w < L; ++w) d = 0.5 * d;
+    const int old = first ? -1 : b.level[i];
+    int now;
+    if (first) now = w;
+    else if (closing) now = old;
+    else if (w > old) now = w;
+    else if (w < old && old > 0 && (T & ((2ull << (L - old)) - 1ull)) == 0ull) now = old - 1;
+    else now = old;
+    double dt_old = dt_max, dt_new = dt_max;
+    for (int l = 0; l < old; ++l) dt_old = 0.5 * dt_old;
+    for (int l = 0; l < now; ++l) dt_new = 0.5 * dt_new;
+    const double kick = first ? 0.5 * dt_new : closing ? 0.5 * dt_old : 0.5 * dt_old + 0.5 * dt_new;
+    const double m = b.m64[i];
+    const double gm = b.G * m;
+    for (int k = 0; k < b.dim; ++k) {
+        const double F = -(gm * b.sums[(size_t)k * b.cap + r]);
+        double v = b.v64[(size_t)k * b.pad + i];
+        v += (F / m) * kick;
+        b.v64[(size_t)k * b.pad + i] = v;
+    }
+    if (now != old) {
+        b.level[i] = now;
+        atomicAdd(&c->pop[now], 1u);
+        if (old >= 0) atomicSub(&c->pop[old], 1u);
+    }
+}
+
+// The controller behind the kick: history, the stops, dn from the deepest level present, T and t.
+__global__ void block_control_post_kernel(BlockClock* __restrict__ c) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (c->stopped) return;
+    uint32_t* const history = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c) + kBlockClockHistoryOffset);
+    const int L = c->levels;
+    int deepest = 0;
+    for (int l = 0; l <= L; ++l) if (c->pop[l]) deepest = l;
+    if (deepest > c->deepest) c->deepest = deepest;
+    c->first = 0;
+    c->pair_terms += (unsigned long long)c->n_active * c->n_total;
+    const bool closing = c->closing != 0, capped = !closing && c->substeps == c->max_substeps;
+    const uint32_t dn = (closing || capped) ? 0u : 1u << (L - deepest);
+    const uint32_t slot = c->recorded;
+    if (slot < c->capacity) { history[2 * (size_t)slot] = c->n_active; history[2 * (size_t)slot + 1] = dn; c->recorded = slot + 1u; }
+    if (closing) { c->finished = 1; c->stopped = 1; return; }
+    if (capped) { c->status = 2; c->stopped = 1; return; }
+    c->dt_drift = (double)dn * c->tick;
+    c->drift = 1;
+    c->T += dn;
+    c->t = c->t_start + (double)c->T * c->tick;
+    c->substeps += 1u;
+}
+
+// x += v * (dn tick) for ALL bodies, the fp32 chunk refreshed: kick_drift_kernel's drift, one lane per (body, component)
+__global__ __launch_bounds__(256) void block_drift_kernel(BlockStepArgs b) {
+    if (b.clock->drift == 0) return;
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= b.count) return;
+    const size_t at = (size_t)blockIdx.y * b.pad + l;
+    double x = b.x64[at];
+    x += b.v64[at] * b.clock->dt_drift;
+    b.x64[at] = x;
+    b.pos_chunk[at] = (float)x;
+}
+
+// select, first half: flags[i] = body i's own step ends at the clock's T
+__global__ __launch_bounds__(256) void block_flag_kernel(BlockStepArgs b) {
+    const BlockClock* const c = b.clock;
+    if (c->stopped) return;
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= b.count) return;
+    b.flags[l] = (c->T & ((1ull << (c->levels - b.level[l])) - 1ull)) == 0ull ? 1u : 0u;
+}
+
+// select, second half, behind the exclusive scan of the flags (in place; the total behind the last one): ascending order
+__global__ __launch_bounds__(256) void block_scatter_kernel(BlockStepArgs b) {
+    BlockClock* const c = b.clock;
+    if (c->stopped) return;
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l == 0) c->n_active = b.flags[b.count];
+    if (l >= b.count) return;
+    const unsigned at = b.flags[l];
+    if (b.flags[l + 1] != at) b.list[at] = (unsigned)l;
+}
+
 __global__ __launch_bounds__(256) void export_forces_kernel(const float* __restrict__ acc, int splits, int dim,
                                                             unsigned pad, size_t count, double G,
                                                             const double* __restrict__ m64,
@@ -486,6 +638,37 @@ hipError_t launch_kick_drift_slots_clock(const SlotKickArgs& k, const StepClock*
     if (k.count == 0) return hipSuccess;
     hipLaunchKernelGGL(kick_drift_slots_clock_kernel, dim3(blocks_for(k.count), (unsigned)k.dim, 1), dim3(256), 0, stream, k, clock);
     return hipGetLastError();
+}
+
+hipError_t launch_block_clock_init(const BlockStepArgs& b, double accel_length, double dt_max, double t_start, int levels, unsigned long long T_end,
+                                   uint32_t max_substeps, uint32_t capacity, hipStream_t stream) {
+    hipLaunchKernelGGL(block_clock_init_kernel, dim3(1), dim3(64), 0, stream, b.clock, accel_length, dt_max, t_start, levels, T_end,
+                       (unsigned long long)b.count, max_substeps, capacity);
+    if (b.count) hipLaunchKernelGGL(block_levels_init_kernel, dim3(blocks_for(b.count)), dim3(256), 0, stream, b.level, b.count);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_kick(const BlockStepArgs& b, hipStream_t stream) {
+    if (b.count) hipLaunchKernelGGL(block_check_kernel, dim3(blocks_for(b.count)), dim3(256), 0, stream, b);
+    hipLaunchKernelGGL(block_control_pre_kernel, dim3(1), dim3(64), 0, stream, b.clock);
+    if (b.count) hipLaunchKernelGGL(block_kick_kernel, dim3(blocks_for(b.count)), dim3(256), 0, stream, b);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_select(const BlockStepArgs& b, hipStream_t stream) {
+    if (b.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(block_flag_kernel, dim3(blocks_for(b.count)), dim3(256), 0, stream, b);
+    hipError_t e = nbx_sort::exclusive_scan(b.flags, b.flags, &b.clock->n_bodies, (unsigned)b.count, b.tile_sums, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(block_scatter_kernel, dim3(blocks_for(b.count)), dim3(256), 0, stream, b);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_advance(const BlockStepArgs& b, hipStream_t stream) {
+    hipLaunchKernelGGL(block_control_post_kernel, dim3(1), dim3(64), 0, stream, b.clock);
+    if (b.count) hipLaunchKernelGGL(block_drift_kernel, dim3(blocks_for(b.count), (unsigned)b.dim, 1), dim3(256), 0, stream, b);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_block_select(b, stream);
 }
 
 hipError_t launch_export_forces(const float* acc, int splits, int dim, unsigned pad, size_t count, double G,

@@ -53,6 +53,7 @@ struct Options {
     double dt_min = 0.0;            // --dt-min: kdka's smallest step (default: --dt / 1024)
     double t_end = std::numeric_limits<double>::infinity();   // --t-end: kdka stops there (default: after --steps steps)
     bool pow2 = false;              // --pow2: kdka's steps are --dt / 2^j
+    int levels = 8;                 // --levels L: kdkb's deepest level, a body's step is --dt / 2^level
     std::string law = "reference";  // --law reference|newton: pair law of the stepping loop (newton: extension, needs --softening)
     double softening = 0.0;         // --softening eps: Plummer-softened law in the stepping loop (extension; 0 = reference law)
     std::vector<int> devices;       // --gpus / --devices: shard the HIP rows over these GPUs (one process)
@@ -625,7 +626,8 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
     }
 
     if (opt.steps > 0 && run_hip) {
-        out << "Leapfrog (kick-drift) on HIP: " << opt.steps << " steps" << (opt.integrator == "kdka" ? " at most (steps chosen on the device)" : "") << ", dt = " << opt.dt << ", G = " << opt.G;
+        out << "Leapfrog (kick-drift) on HIP: " << opt.steps << " steps" << (opt.integrator == "kdka" ? " at most (steps chosen on the device)" : opt.integrator == "kdkb" ? " (blocks of dt; a body steps by dt / 2^level, level chosen on the device)" : "")
+            << ", dt = " << opt.dt << ", G = " << opt.G;
         if (opt.softening > 0.0) out << ", softening = " << opt.softening;
         if (opt.law != "reference") out << ", law = " << opt.law;
         if (opt.integrator != "kd") out << ", integrator = " << opt.integrator;
@@ -638,6 +640,12 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
         nbx_step_clock ctx_clock{};
         double ctx_dt_smallest = 0.0, ctx_dt_largest = 0.0;
         unsigned ctx_taken = 0;
+        // --integrator kdkb: chained calls of --energy-every blocks of --dt with block time steps (nbx_ctx_step_kdk_block); the row is
+        // Leapfrog_HIP_<n>blocks_kdkb and a line behind the loop gives the substeps, the pair terms next to a shared step's, the deepest level
+        const bool ctx_kdkb = opt.integrator == "kdkb";
+        unsigned long long blk_substeps = 0, blk_terms = 0, blk_shared = 0;
+        int blk_deepest = 0, blk_status = 0;
+        double blk_t = 0.0;
         const long long us = safely_execute(log, "Leapfrog_HIP", [&] {
             HipSimulation<D> sim(bodies, opt.G, opt.softening, opt.law == "newton");
             double ke = 0.0, pe = 0.0, e0 = 0.0;
@@ -663,6 +671,14 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                     done += static_cast<int>(ctx_clock.steps);
                     if (ctx_clock.finished || ctx_clock.status || ctx_clock.steps == 0) done = opt.steps;   // the last energy line, then out
                     ctx_clock.steps = ctx_taken;
+                } else if (ctx_kdkb) {   // chained calls of k blocks: each ends with every body at one time, the next starts from fresh levels
+                    nbx_block_control control{};
+                    control.accel_length = opt.accel_length; control.dt_max = opt.dt; control.t_start = done * opt.dt; control.levels = opt.levels;
+                    const nbx_block_clock clock = sim.step_kdk_block(control, k);
+                    blk_substeps += clock.substeps; blk_terms += clock.pair_terms;
+                    blk_shared += (static_cast<unsigned long long>(clock.substeps) + 1ull) * static_cast<unsigned long long>(n) * static_cast<unsigned long long>(n);
+                    blk_deepest = std::max(blk_deepest, clock.deepest_level); blk_status = clock.status; blk_t = clock.t;
+                    done = clock.status ? opt.steps : done + k;
                 } else {
                     if (opt.integrator == "kdk") sim.step_kdk(opt.dt, k); else sim.step(opt.dt, k);
                     done += k;
@@ -682,12 +698,17 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
         });
         if (us >= 0) {
             const double seconds = static_cast<double>(us) / 1e6;
-            csv << "Leapfrog_HIP_" << opt.steps << "steps" << (ctx_kdka ? "_kdka" : "") << "," << n << "," << D;
+            if (ctx_kdkb) csv << "Leapfrog_HIP_" << opt.steps << "blocks_kdkb," << n << "," << D;
+            else csv << "Leapfrog_HIP_" << opt.steps << "steps" << (ctx_kdka ? "_kdka" : "") << "," << n << "," << D;
             write_time(csv, seconds);
             if (opt.accuracy) csv << ",";
             csv << std::endl;
             out << "Time taken: " << seconds << " s (" << seconds / opt.steps << " s/step; force kernels " << kernel_s << " s per rank)" << std::endl;
             if (ctx_kdka) adaptive_line(ctx_clock.steps, ctx_clock.t, ctx_dt_smallest, ctx_dt_largest, ctx_clock.finished != 0);
+            if (ctx_kdkb)
+                out << "Block steps: " << blk_substeps << " substeps, t = " << std::setprecision(12) << blk_t << std::setprecision(6) << ", pair terms " << blk_terms
+                    << " (a shared step: " << blk_shared << ", " << static_cast<double>(blk_shared) / static_cast<double>(blk_terms ? blk_terms : 1) << " x), deepest level "
+                    << blk_deepest << " of " << opt.levels << (blk_status == 1 ? "; stopped: an acceleration was not finite" : "") << std::endl;
             if (!opt.dump.empty()) dump_raw(opt.dump + "_Leapfrog_HIP.f64", state);
             out << "Body #1 position: (";
             for (int d = 0; d < D; ++d) out << state[0].position[d] << (d < D - 1 ? ", " : "");
@@ -722,6 +743,9 @@ void usage(const char* argv0) {
               << "                      acceleration of the evaluation just made; --dt is the largest step, --steps the cap, rows carry _kdka" << std::endl
               << "      --accel-length <c> kdka's c (a length: eta^2 x softening is the usual choice); --dt-min <t> its smallest step (default --dt / 1024);" << std::endl
               << "                      --t-end <t> where it stops (default: after --steps steps); --pow2: its steps are --dt / 2^j" << std::endl
+              << "                      kdkb (-m g on one GPU, needs --softening) = kick-drift-kick with block time steps: --steps blocks of --dt, a body steps by" << std::endl
+              << "                      --dt / 2^level with its level in [0, --levels L] (default 8) chosen on the device from its own acceleration and --accel-length;" << std::endl
+              << "                      only the bodies whose step ends are evaluated; the row is Leapfrog_HIP_<n>blocks_kdkb" << std::endl
               << "      --law <reference|newton> Pair law of the stepping loop: the reference's r^-4 form (default) or the attractive" << std::endl
               << "                      softened Newtonian law (extension; needs --softening; Plummer velocities then use --G)" << std::endl
               << "                      with -m t: BarnesHut_HIP_newton rows behind the reference-law rows, judged against the all-pairs forces" << std::endl
@@ -802,8 +826,8 @@ int main(int argc, char* argv[]) {
             opt.softening = std::stod(argv[++i]);
         } else if (arg == "--integrator" && has_value) {
             opt.integrator = argv[++i];
-            if (opt.integrator != "kd" && opt.integrator != "kdk" && opt.integrator != "kdka") {
-                std::cerr << "Error: --integrator must be kd, kdk or kdka" << std::endl;
+            if (opt.integrator != "kd" && opt.integrator != "kdk" && opt.integrator != "kdka" && opt.integrator != "kdkb") {
+                std::cerr << "Error: --integrator must be kd, kdk, kdka or kdkb" << std::endl;
                 return 1;
             }
         } else if (arg == "--accel-length" && has_value) {
@@ -814,6 +838,8 @@ int main(int argc, char* argv[]) {
             opt.t_end = std::stod(argv[++i]);
         } else if (arg == "--pow2") {
             opt.pow2 = true;
+        } else if (arg == "--levels" && has_value) {
+            opt.levels = std::stoi(argv[++i]);
         } else if (arg == "--law" && has_value) {
             opt.law = argv[++i];
             if (opt.law != "reference" && opt.law != "newton") {
@@ -879,6 +905,16 @@ int main(int argc, char* argv[]) {
         }
         if (!(opt.accel_length > 0.0)) {
             std::cerr << "Error: --integrator kdka needs --accel-length c > 0 (dt = sqrt(c / a_max))" << std::endl;
+            return 1;
+        }
+    }
+    if (opt.integrator == "kdkb") {
+        if (opt.methods.find('g') == std::string::npos || opt.methods.find_first_of("atp") != std::string::npos || opt.devices.size() > 1) {
+            std::cerr << "Error: --integrator kdkb drives the all-pairs loop on one GPU (-m g): leave --gpus / --devices out" << std::endl;
+            return 1;
+        }
+        if (!(opt.accel_length > 0.0) || !(opt.softening > 0.0) || opt.levels < 0 || opt.levels > 20) {
+            std::cerr << "Error: --integrator kdkb needs --accel-length c > 0, --softening eps > 0 and --levels in [0, 20]" << std::endl;
             return 1;
         }
     }

@@ -265,6 +265,15 @@ double HipSimulation<D>::max_accel() {
     return a;
 }
 template <int D>
+nbx_block_clock HipSimulation<D>::step_kdk_block(const nbx_block_control& control, int n_blocks, int max_substeps) {
+    if (!ctx_) throw std::runtime_error("HipSimulation::step_kdk_block: the simulation is sharded over several devices; block time steps need one GPU");
+    nbx_block_clock clock{};
+    int rc = nbx_ctx_step_kdk_block(ctx_, G_, &control, n_blocks, max_substeps);
+    if (!rc && n_blocks > 0) rc = nbx_ctx_get_block_clock(ctx_, &clock);
+    if (rc != NBX_OK) raise("HipSimulation::step_kdk_block", rc);
+    return clock;
+}
+template <int D>
 void HipSimulation<D>::step_range(double& dt_smallest, double& dt_largest) {
     if (!ctx_) throw std::runtime_error("HipSimulation::step_range: the simulation is sharded over several devices; steps chosen on the device need one GPU");
     dt_smallest = dt_largest = 0.0;

@@ -74,6 +74,10 @@ public:
     // device, computing one first when there is none (nbx_ctx_max_accel).  One GPU only: on a simulation sharded over several
     // devices (set_hip_devices) both throw std::runtime_error -- the sharded loop needs an all-reduce of the maximum.
     nbx_step_clock step_kdk_adaptive(const nbx_step_control& control, int max_steps);
+    // extension: kick-drift-kick with block time steps over n_blocks steps of control.dt_max (nbx_ctx_step_kdk_block): a body steps by
+    // dt_max / 2^level, only the bodies whose step ends are evaluated; returns the device's clock (which synchronises).  One GPU, a
+    // softening length > 0.
+    nbx_block_clock step_kdk_block(const nbx_block_control& control, int n_blocks, int max_substeps = 1 << 20);
     double max_accel();
     void step_range(double& dt_smallest, double& dt_largest);   // over the steps of the last step_kdk_adaptive call (0, 0: it took none)
     void energy(double& kinetic, double& potential);  // of the whole system, under the reference law's potential
