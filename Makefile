@@ -22,7 +22,7 @@ all: lib oracle nbody_sim
 lib: $(LIB)
 
 OBJS := $(addprefix $(CSRC)/,$(addsuffix $(O),force_kernel force_sym_kernel force_launch state_kernels nbx_api nbx_node leaf_pair_kernel \
-          leaf_plan_api leaf_far_kernel leaf_phi_kernel octree_device close_hash measure_kernels active_kernel))
+          leaf_plan_api leaf_far_kernel leaf_phi_kernel octree_device close_hash measure_kernels active_kernel active_jerk_kernel))
 # name of the force-kernel variant used when the caller does not pick one
 # (round 4: the three-level summation build -- same pair arithmetic, fp32 errors ~3x smaller for +1.5 % time)
 DEFAULT_VARIANT ?= fastpk3l_t8_w3_u4
@@ -49,6 +49,10 @@ $(CSRC)/state_kernels$(O): $(CSRC)/state_kernels.hip $(CSRC)/nbx_internal.h $(CS
 
 # forces on a device-resident list of targets: the force kernels' flags
 $(CSRC)/active_kernel$(O): $(CSRC)/active_kernel.hip $(CSRC)/nbx_internal.h
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+# the same evaluation with the jerk (fourth-order Hermite): active_kernel's flags
+$(CSRC)/active_jerk_kernel$(O): $(CSRC)/active_jerk_kernel.hip $(CSRC)/nbx_internal.h
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/nbx_api$(O): $(CSRC)/nbx_api.hip $(CSRC)/nbx_internal.h $(CSRC)/nbx_ctx.h $(CSRC)/device_block.h include/nbody_hip.h Makefile

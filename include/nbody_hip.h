@@ -633,6 +633,74 @@ int nbx_ctx_get_block_clock(nbx_ctx* ctx, nbx_block_clock* clock);
 int nbx_ctx_get_block_history(nbx_ctx* ctx, uint32_t* n_active_out, uint32_t* ticks_out, size_t capacity, size_t* count);
 int nbx_ctx_get_block_levels(nbx_ctx* ctx, int32_t* levels_out);
 
+/* EXTENSION: accelerations and their time derivatives (jerks) of a list of targets -- nbx_ctx_compute_accel_active's twin for
+ * fourth-order schemes.  For every r < n_targets, over ALL n_total bodies at the positions AND velocities the context holds now:
+ *       A_r = sum_j m_j w d,     J_r = sum_j m_j w [ dv - p (d.dv) / rho^2 d ],
+ *       d = p_j - p_r,  dv = v_j - v_r,  rho^2 = r^2 + eps^2,  w = rho^-p,  p = 4 (the softened reference law) or 3 (NBX_FORCE_LAW_NEWTON):
+ * J is the exact time derivative of A along straight paths.  The pair arithmetic, the summation (fp32 over a tile of 256 sources, the
+ * tiles in fp64, no floating-point atomics), the two builds -- one target per lane for a short list, four for a long one -- and
+ * NBODY_HIP_ACTIVE_LONG_LIST are nbx_ctx_compute_accel_active's; the sources' velocities are the fp32 roundings of the context's,
+ * refreshed by the call.  A coincident pair with different velocities contributes the finite term m dv / eps^p.  An OBSERVER: bodies,
+ * accelerations and clocks are untouched.  (It shares the device's target list with nbx_ctx_compute_accel_active: each of the two
+ * compute calls ends the validity of the other's results.)
+ * nbx_ctx_get_accel_jerk_active: row r of accel_out / jerk_out (n_targets x Vector<dim>, list order; either may be null) =
+ * -(G' A_r) and -(G' J_r), G' = G under the reference law and -G under NBX_FORCE_LAW_NEWTON: the acceleration F / m that the
+ * context's kicks apply to body targets[r] and its time derivative -- accelerations, not forces, so that a massless tracer keeps its
+ * row.  Synchronises the stream.
+ * Refusals: nbx_ctx_compute_accel_active's, word for word; nbx_ctx_get_accel_jerk_active is NBX_ERR_STATE without a preceding
+ * nbx_ctx_compute_accel_jerk_active (an upload, the other compute call or a block-step call ends its validity). */
+int nbx_ctx_compute_accel_jerk_active(nbx_ctx* ctx, const uint32_t* targets, size_t n_targets);
+int nbx_ctx_get_accel_jerk_active(nbx_ctx* ctx, double G, double* accel_out, double* jerk_out);
+
+/* EXTENSION: the fourth-order HERMITE scheme with block time steps.  Body i has its own step dt_max 2^-level_i, its own time t_i and
+ * (x, v, a, j) at that time; ALL bodies are predicted to the current time (O(N)); accelerations and jerks are computed, through
+ * nbx_ctx_compute_accel_jerk_active's kernels, only for the bodies whose own step ends (O(n_active N)), and those are corrected.
+ * tick, dt_l, T_end, want(raw) and the level rule are nbx_ctx_step_kdk_block's.  The rule, in fp64 without contraction
+ * (a = -(G' A), j = -(G' J) as above; |.| the Euclidean length, squares added in component order):
+ *       evaluation 0 (T = 0, all bodies): (a, j) from x, v.  Any component not finite: status = 1; stop.
+ *           raw_i = eta_start |a_i| / |j_i|   (+infinity when |j_i| == 0);  level_i = want(raw_i);  t_i = 0
+ *       after every evaluation: record (n_active, dn);  pair_terms += n_active n_total
+ *           T == T_end: finished = 1; stop.     substeps == max_substeps: status = 2; stop.
+ *           dn = 2^(L - deepest level present);  T += dn;  t = t_start + T tick;  substeps += 1
+ *       predict ALL bodies, h = (T - t_i) tick:
+ *           xp = x + v h + a h^2/2 + j h^3/6,   vp = v + a h + j h^2/2
+ *           the fp32 positions and velocities (the kernels' sources) are written from xp, vp; x, v themselves stay
+ *       active = { i : T % 2^(L - level_i) == 0 };  (a1, j1) of the active bodies from the predicted fp32 positions and velocities
+ *       any component not finite: status = 1; stop; nobody is corrected
+ *       correct the active bodies, h = dt_level_i:
+ *           v1 = v + (h/2)(a + a1) + (h^2/12)(j - j1)
+ *           x1 = x + (h/2)(v + v1) + (h^2/12)(a - a1)
+ *           a2 = (-6 (a - a1) - h (4 j + 2 j1)) / h^2
+ *           a3 = (12 (a - a1) + 6 h (j + j1)) / h^3
+ *           a2e = a2 + h a3
+ *           raw = sqrt( eta (|a1| |a2e| + |j1|^2) / (|j1| |a3| + |a2e|^2) )       (+infinity when the denominator is 0)
+ *           w = want(raw):  new = w if w > old;  old - 1 if w < old and old > 0 and T % 2^(L-old+1) == 0;  old otherwise;  at T_end: old
+ *           (x, v, a, j, t_i, level_i) = (x1, v1, a1, j1, T, new);  the fp32 position and velocity of i are written from x1, v1
+ * Every body is active at T_end, so afterwards the context's bodies and its fp32 sources are the corrected state at ONE time:
+ * nbx_ctx_energy and a download see it.  levels = 0 is the shared-step Hermite scheme with dt_max.  A later call starts afresh
+ * (evaluation 0, fresh levels).
+ * TIME LEVELS: after status == 2 (max_substeps reached before T_end) the bodies are NOT at one time: body i's x and v are at its own
+ * t_i, the end of its last own step (the fp32 sources are put back to their roundings), and a later call does not resume this one.
+ * After status == 1 the loop stopped before anybody
+ * was corrected with the sums that were not finite.  Afterwards the context holds no valid accelerations (nbx_ctx_get_forces is
+ * refused).
+ * The call is asynchronous and reads nothing back to choose anything; it stops queueing through nbx_ctx_step_kdk_block's window of
+ * 4-byte looks (NBODY_HIP_STEP_WINDOW), and the results do not depend on it.
+ * nbx_ctx_get_block_clock / _history / _levels report the last block-step call of EITHER kind.  A Hermite call counts evaluation 0:
+ * evaluations == substeps + 1 when it finishes or meets the cap.
+ * Refusals, before anything is launched.  NBX_ERR_INVALID (all of these need no device): a null control, a field outside the range
+ * given with it, reserved != 0, n_blocks < 0, max_substeps < 0 or > 1 << 20; a null context.  NBX_ERR_STATE: nothing uploaded, a
+ * context with n_shards != 1, softening 0.  n_blocks == 0 does nothing and leaves no clock. */
+typedef struct nbx_hermite_control {
+    double eta;            /* accuracy parameter of Aarseth's criterion: > 0, finite */
+    double eta_start;      /* the same for the first step, chosen from |a| / |j| alone: > 0, finite */
+    double dt_max;         /* > 0, finite */
+    double t_start;        /* finite */
+    int    levels;         /* L in [0, 20] */
+    int    reserved;       /* must be 0 */
+} nbx_hermite_control;
+int nbx_ctx_step_hermite_block(nbx_ctx* ctx, double G, const nbx_hermite_control* control, int n_blocks, int max_substeps);
+
 /* Forces of this shard's targets as Vector<dim>[count] doubles: F_i = -(G m_i) a_i.  count = this shard's bodies: shard_len, or
  * fewer -- possibly none -- for the last shards (a shard g with g * shard_len >= n_total is empty); exactly count rows are written.
  * Synchronises the stream. */

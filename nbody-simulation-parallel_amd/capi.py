@@ -97,6 +97,9 @@ ABI = [
     ("nbx_ctx_get_block_clock", _i, [_vp, _vp]),
     ("nbx_ctx_get_block_history", _i, [_vp, _vp, _vp, _sz, _c.POINTER(_sz)]),
     ("nbx_ctx_get_block_levels", _i, [_vp, _vp]),
+    ("nbx_ctx_compute_accel_jerk_active", _i, [_vp, _vp, _sz]),
+    ("nbx_ctx_get_accel_jerk_active", _i, [_vp, _d, _vp, _vp]),
+    ("nbx_ctx_step_hermite_block", _i, [_vp, _d, _vp, _i, _i]),
     ("nbx_ctx_get_forces", _i, [_vp, _d, _vp]),
     ("nbx_ctx_accuracy", _i, [_vp, _d, _vp, _pd]),
     ("nbx_ctx_get_accel", _i, [_vp, _vp]),
@@ -249,6 +252,11 @@ class StepClock(ctypes.Structure):
 class BlockControl(ctypes.Structure):
     """nbx_block_control of include/nbody_hip.h: how nbx_ctx_step_kdk_block chooses its levels."""
     _fields_ = [("accel_length", _d), ("dt_max", _d), ("t_start", _d), ("levels", _i), ("reserved", _i)]
+
+
+class HermiteControl(ctypes.Structure):
+    """nbx_hermite_control of include/nbody_hip.h: how nbx_ctx_step_hermite_block chooses its levels."""
+    _fields_ = [("eta", _d), ("eta_start", _d), ("dt_max", _d), ("t_start", _d), ("levels", _i), ("reserved", _i)]
 
 
 class BlockClock(ctypes.Structure):
@@ -790,6 +798,30 @@ class Context:
         out = np.zeros(self.count, dtype=np.int32)
         self._ck(self.lib.nbx_ctx_get_block_levels(self.h, out.ctypes.data if self.count else None), "nbx_ctx_get_block_levels")
         return out
+
+    def compute_accel_jerk_active(self, targets):
+        """The acceleration and jerk sums of the listed bodies against all bodies, from the positions and velocities the context holds
+        (nbx_ctx_compute_accel_jerk_active): any order, repeats allowed, an observer of the context.  Single shard, softening > 0."""
+        t = np.ascontiguousarray(targets, dtype=np.uint32).reshape(-1)
+        self._ck(self.lib.nbx_ctx_compute_accel_jerk_active(self.h, t.ctypes.data if t.size else None, t.size), "nbx_ctx_compute_accel_jerk_active")
+        self._jerk_rows = int(t.size)
+
+    def accel_jerk_active(self, G: float = REFERENCE_G):
+        """(a[n_targets, dim], da/dt[n_targets, dim]) of the last compute_accel_jerk_active, in list order: the accelerations F / m as
+        the context's kicks use them (nbx_ctx_get_accel_jerk_active)."""
+        a = np.empty((getattr(self, "_jerk_rows", 0), self.dim), dtype=np.float64)
+        j = np.empty_like(a)
+        self._ck(self.lib.nbx_ctx_get_accel_jerk_active(self.h, float(G), a.ctypes.data, j.ctypes.data), "nbx_ctx_get_accel_jerk_active")
+        return a, j
+
+    def step_hermite_block(self, eta: float, dt_max: float, levels: int, n_blocks: int = 1, max_substeps: int = 1 << 20, t_start: float = 0.0,
+                           G: float = REFERENCE_G, eta_start: float = 0.01) -> "BlockClock":
+        """Fourth-order Hermite over n_blocks steps of dt_max with block time steps: body i steps by dt_max / 2^level_i, its level chosen
+        on the device by Aarseth's criterion, all bodies are predicted and only those whose step ends are evaluated and corrected
+        (nbx_ctx_step_hermite_block).  Returns the clock (which synchronises); block_history and block_levels report this call."""
+        k = HermiteControl(float(eta), float(eta_start), float(dt_max), float(t_start), int(levels), 0)
+        self._ck(self.lib.nbx_ctx_step_hermite_block(self.h, float(G), ctypes.byref(k), int(n_blocks), int(max_substeps)), "nbx_ctx_step_hermite_block")
+        return self.block_clock() if int(n_blocks) > 0 else None
 
     def forces(self, G: float = REFERENCE_G) -> np.ndarray:
         out = np.empty((self.count, self.dim), dtype=np.float64)

@@ -9,7 +9,7 @@
 // itself: the list may be in any order and may repeat an index.
 //
 // The host knows neither n nor which shape fits it, so it queues BOTH builds for the list's capacity and each returns at once
-// unless n is on its side of ActiveArgs::long_list (active_layout below is all either needs):
+// unless n is on its side of ActiveArgs::long_list (nbx_internal.h's active_layout is all either needs):
 //   TPL = 1  the short list -- the two bodies of a binary against a million sources.  One target per lane, 256 per list block, and
 //            the sources cut into as many slices as the buffer allows, up to 256 (the mixed mode's fp64 list pass has this layout).
 //   TPL = 8  the long list -- a synchronisation point, every body active.  K1's shape: four float2 target pairs per lane, packed
@@ -28,22 +28,6 @@ namespace nbx {
 namespace {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
-
-// What a launch looks like for the list as it stands: n targets, `stride` doubles between the component planes of a slice (n in
-// whole blocks of 256), as many source slices as the buffer holds (at most the grid's), `tps` source tiles per slice.
-struct ActiveLayout { unsigned n, stride, slices, tps; };
-__device__ __forceinline__ ActiveLayout active_layout(const ActiveArgs& a, int dim) {
-    ActiveLayout s;
-    const unsigned listed = *a.count;
-    s.n = listed < a.cap ? listed : a.cap;
-    s.stride = s.n ? (s.n + 255u) / 256u * 256u : 256u;
-    unsigned long long fit = a.budget / ((unsigned long long)dim * s.stride);
-    if (fit > (unsigned long long)a.max_slices) fit = (unsigned long long)a.max_slices;
-    s.slices = fit ? (unsigned)fit : 1u;
-    const unsigned tiles = a.pad / (unsigned)kTile;
-    s.tps = (tiles + s.slices - 1u) / s.slices;
-    return s;
-}
 
 template <int D, int TPL, int NEWTON>
 __global__ __launch_bounds__(256, TPL > 1 ? 3 : 4) void active_accel_kernel(ActiveArgs a) {

@@ -166,6 +166,8 @@ constexpr int kStepWindowDefault = 2;
 // lists of at least this many targets run the long-list build of active_kernel.hip (NBODY_HIP_ACTIVE_LONG_LIST in
 // [1, 2^31] overrides)
 constexpr unsigned kActiveLongListDefault = 2048;
+// the same for active_jerk_kernel.hip, whose builds cross between 512 and 1,024 targets; the same override
+constexpr unsigned kJerkLongListDefault = 1024;
 constexpr int kGraphMinSteps = 4;   // nbx_ctx_step replays a captured step from this many steps on
 // Mixed mode: selection rule |a|^2 < (sigma u / tol)^2 Q (force_kernel.hip).  The sigma factor is a calibration of the DEFAULT
 // kernel's summation (round 4: the three-level kernel, whose rounding errors are ~3x smaller than the two-level kernel's at the same
@@ -533,7 +535,7 @@ int upload_finish(nbx_ctx* c, const unsigned long long facts[3]) {
     }
     c->uploaded = true;
     c->have_accel = false;
-    c->have_active = false;
+    c->have_active = false; c->have_jerk = false;
     c->tgt_cand_valid = 0; c->bad_list_pass = -1;
     c->probe_bad = 0;
     c->counters_pending = false; c->steps_since_poll = 0; c->last_cand = c->last_bad = 0;
@@ -681,7 +683,8 @@ int nbx_ctx_create(nbx_ctx** out, int device, int dim, size_t n_total, int n_sha
         const char* e = std::getenv("NBODY_HIP_ACTIVE_LONG_LIST");
         char* end = nullptr;
         const long long w = e && *e ? std::strtoll(e, &end, 10) : 0;
-        if (end && *end == '\0' && w >= 1 && w <= (1ll << 31)) c->active_long_list = (unsigned)w;
+        c->jerk_long_list = kJerkLongListDefault;
+        if (end && *end == '\0' && w >= 1 && w <= (1ll << 31)) c->active_long_list = c->jerk_long_list = (unsigned)w;
     }
 #define CTX_TRY(expr)                                                            \
     do {                                                                         \
@@ -745,7 +748,8 @@ int nbx_ctx_destroy(nbx_ctx* c) {
     if (c->clock_block) (void)hipFree(c->clock_block);
     if (c->amax_word) (void)hipFree(c->amax_word);
     for (void* p : {(void*)c->active_list, (void*)c->active_count, (void*)c->active_part, (void*)c->active_sums, (void*)c->block_clock,
-                    (void*)c->block_level, (void*)c->block_flags, (void*)c->block_tile_sums})
+                    (void*)c->block_level, (void*)c->block_flags, (void*)c->block_tile_sums, (void*)c->vel_all, (void*)c->jerk_part,
+                    (void*)c->jerk_sums, (void*)c->hermite_a, (void*)c->hermite_j, (void*)c->hermite_t})
         if (p) (void)hipFree(p);
     if (c->stop_ring) (void)hipHostFree(c->stop_ring);
     for (auto e : c->stop_ev) if (e) (void)hipEventDestroy(e);
@@ -1331,7 +1335,7 @@ static int ctx_fit_active(nbx_ctx* c, size_t want_cap) {
         for (void** p : {(void**)&c->active_list, (void**)&c->active_part, (void**)&c->active_sums}) { HIP_TRY(hipFree(*p)); *p = nullptr; }
         c->active_cap = 0;
     }
-    c->have_active = false;
+    c->have_active = false; c->have_jerk = false;
     const unsigned long long cap_r = ((unsigned long long)want_cap + 255ull) / 256ull * 256ull;
     const unsigned long long max_slices = c->pad / kTile < 256u ? c->pad / kTile : 256u;
     unsigned long long whole = (1ull << 21) / cap_r;
@@ -1382,7 +1386,7 @@ int nbx_ctx_compute_accel_active(nbx_ctx* c, const uint32_t* targets, size_t n_t
     HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's list is borrowed only for this call; the kernels below run asynchronously
     HIP_TRY(launch_active_accel(active_args(c, c->active_count, nullptr), c->stream));
     c->active_n = n_targets;
-    c->have_active = true;
+    c->have_active = true; c->have_jerk = false;
     return NBX_OK;
 }
 
@@ -1459,7 +1463,7 @@ int nbx_ctx_step_kdk_block(nbx_ctx* c, double G, const nbx_block_control* contro
                                     (unsigned long long)n_blocks << control->levels, (uint32_t)max_substeps, (uint32_t)max_substeps + 1u, s));
     HIP_TRY(launch_block_select(b, s));   // T = 0, every level 0: all bodies
     c->block_valid = true;
-    c->have_active = false;               // the list and its sums are the loop's now
+    c->have_active = false; c->have_jerk = false;              // the list and its sums are the loop's now
     c->have_accel = false;
     c->tgt_cand_valid = 0; c->bad_list_pass = -1;
     const ActiveArgs A = active_args(c, &b.clock->n_active, &b.clock->stopped);
@@ -1531,6 +1535,150 @@ int nbx_ctx_get_block_levels(nbx_ctx* c, int32_t* levels_out) {
     if (rc) return rc;
     if (c->count) HIP_TRY(hipMemcpyAsync(levels_out, c->block_level, c->count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return NBX_OK;
+}
+
+// ---- accelerations and jerks of a list of targets; fourth-order Hermite with block time steps (include/nbody_hip.h has the rule) ----
+// Room for a list of `want_cap` targets with 2 dim sums each: ctx_fit_active's list and its sizing of the slice sums, twice the planes;
+// the fp32 velocity chunk (pads zero for good: only the real bodies are ever written).
+static int ctx_fit_jerk(nbx_ctx* c, size_t want_cap) {
+    int rc = ctx_fit_active(c, want_cap);
+    if (rc) return rc;
+    if (!c->vel_all) {
+        const size_t bytes = (size_t)c->dim * c->pad * sizeof(float);
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->vel_all), bytes));
+        HIP_TRY(hipMemsetAsync(c->vel_all, 0, bytes, c->stream));
+    }
+    if (c->jerk_part && c->jerk_cap == c->active_cap) return NBX_OK;
+    if (c->jerk_part) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (void** p : {(void**)&c->jerk_part, (void**)&c->jerk_sums}) { HIP_TRY(hipFree(*p)); *p = nullptr; }
+        c->jerk_cap = 0;
+    }
+    c->have_jerk = false;
+    c->jerk_budget = 2ull * c->active_budget;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->jerk_part), c->jerk_budget * sizeof(double)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->jerk_sums), 2 * (size_t)c->dim * c->active_cap * sizeof(double)));
+    c->jerk_cap = c->active_cap;
+    return NBX_OK;
+}
+
+static ActiveArgs jerk_args(const nbx_ctx* c, const unsigned* count, const int* stopped) {
+    ActiveArgs a = active_args(c, count, stopped);
+    a.part = c->jerk_part; a.sums = c->jerk_sums; a.budget = c->jerk_budget; a.long_list = c->jerk_long_list;
+    return a;
+}
+
+static HermiteArgs hermite_args(const nbx_ctx* c, double G) {
+    HermiteArgs h = {};
+    BlockStepArgs& b = h.b;
+    b.clock = reinterpret_cast<BlockClock*>(c->block_clock);
+    b.level = c->block_level; b.list = c->active_list; b.flags = c->block_flags; b.tile_sums = c->block_tile_sums;
+    b.sums = c->jerk_sums; b.cap = c->active_cap; b.dim = c->dim; b.pad = c->pad; b.count = c->count;
+    b.G = c->law ? -G : G; b.absG = std::fabs(G);
+    b.x64 = c->x64; b.v64 = c->v64; b.m64 = c->m64;
+    b.pos_chunk = c->pos_all + (size_t)c->shard * c->dim * c->pad;
+    h.sums = c->jerk_sums; h.a64 = c->hermite_a; h.j64 = c->hermite_j; h.t_i = c->hermite_t; h.vel_chunk = c->vel_all;
+    return h;
+}
+
+int nbx_ctx_compute_accel_jerk_active(nbx_ctx* c, const uint32_t* targets, size_t n_targets) {
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    if (!targets && n_targets) return fail(NBX_ERR_INVALID, "null argument");
+    if (n_targets > ((size_t)1 << 31)) return fail(NBX_ERR_INVALID, "n_targets too large");
+    for (size_t r = 0; r < n_targets; ++r)
+        if (targets[r] >= c->n_total) return fail(NBX_ERR_INVALID, "a target index is >= n_total");
+    int rc = active_state_refusal(c, "nbx_ctx_compute_accel_jerk_active");
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ctx_fit_jerk(c, n_targets))) return rc;
+    const unsigned n32 = (unsigned)n_targets;
+    if (n_targets) HIP_TRY(hipMemcpyAsync(c->active_list, targets, n_targets * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->active_count, &n32, sizeof n32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's list is borrowed only for this call; the kernels below run asynchronously
+    HIP_TRY(launch_hermite_refresh_velocities(hermite_args(c, 0.0), c->stream));
+    HIP_TRY(launch_active_accel_jerk(jerk_args(c, c->active_count, nullptr), c->vel_all, c->stream));
+    c->jerk_n = n_targets;
+    c->have_jerk = true;
+    c->have_active = false;                     // the list and its length word are this call's now
+    return NBX_OK;
+}
+
+int nbx_ctx_get_accel_jerk_active(nbx_ctx* c, double G, double* accel_out, double* jerk_out) {
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    if (!c->have_jerk) return fail(NBX_ERR_STATE, "no accelerations and jerks of a target list on the device (nbx_ctx_compute_accel_jerk_active)");
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t rows = c->jerk_n * c->dim, bytes = rows * sizeof(double);
+    if ((rc = ensure_stage(c, bytes ? 2 * bytes : 8))) return rc;
+    HIP_TRY(launch_active_jerk_export(jerk_args(c, c->active_count, nullptr), c->law ? -G : G, accel_out ? c->stage : nullptr,
+                                      jerk_out ? c->stage + rows : nullptr, c->stream));
+    if (bytes && accel_out) HIP_TRY(hipMemcpyAsync(accel_out, c->stage, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (bytes && jerk_out) HIP_TRY(hipMemcpyAsync(jerk_out, c->stage + rows, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return NBX_OK;
+}
+
+static const char* hermite_control_fault(const nbx_hermite_control* k) {
+    if (!(k->eta > 0.0) || !std::isfinite(k->eta)) return "eta must be finite and > 0";
+    if (!(k->eta_start > 0.0) || !std::isfinite(k->eta_start)) return "eta_start must be finite and > 0";
+    if (!(k->dt_max > 0.0) || !std::isfinite(k->dt_max)) return "dt_max must be finite and > 0";
+    if (!std::isfinite(k->t_start)) return "t_start must be finite";
+    if (k->levels < 0 || k->levels > 20) return "levels must be in [0, 20]";
+    if (k->reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
+// Per evaluation e = 0 .. max_substeps the stream gets: both builds of the list kernel with the jerk and the fold (each reads the
+// active list's length where the select left it), the check, the controller's first half, the start or the corrector of the active
+// bodies, the controller's second half, the predictor of all bodies, the select of the next list.  Clock, controllers, select and
+// the window of looks are nbx_ctx_step_kdk_block's.
+int nbx_ctx_step_hermite_block(nbx_ctx* c, double G, const nbx_hermite_control* control, int n_blocks, int max_substeps) {
+    if (!control) return fail(NBX_ERR_INVALID, "null argument");
+    if (const char* why = hermite_control_fault(control)) return fail(NBX_ERR_INVALID, why);
+    if (n_blocks < 0) return fail(NBX_ERR_INVALID, "n_blocks < 0");
+    if (max_substeps < 0 || max_substeps > (1 << 20)) return fail(NBX_ERR_INVALID, "max_substeps must be in [0, 1 << 20]");
+    if (!c) return fail(NBX_ERR_INVALID, "ctx is null");
+    int rc = active_state_refusal(c, "nbx_ctx_step_hermite_block");
+    if (rc) return rc;
+    if (n_blocks == 0) return NBX_OK;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ctx_fit_jerk(c, c->count))) return rc;
+    if ((rc = ctx_fit_block(c, max_substeps))) return rc;
+    if (!c->hermite_a) {   // a context's count never changes
+        const size_t plane = (size_t)c->dim * c->pad * sizeof(double);
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->hermite_a), plane));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->hermite_j), plane));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->hermite_t), (c->count ? c->count : 1) * sizeof(unsigned long long)));
+    }
+    hipStream_t s = c->stream;
+    HermiteArgs h = hermite_args(c, G);
+    h.eta = control->eta; h.eta_start = control->eta_start;
+    const BlockStepArgs& b = h.b;
+    HIP_TRY(launch_block_clock_init(b, control->eta, control->dt_max, control->t_start, control->levels,
+                                    (unsigned long long)n_blocks << control->levels, (uint32_t)max_substeps, (uint32_t)max_substeps + 1u, s));
+    HIP_TRY(launch_block_select(b, s));   // T = 0, every level 0: all bodies
+    HIP_TRY(launch_hermite_refresh_velocities(h, s));
+    c->block_valid = true;
+    c->have_active = false; c->have_jerk = false;   // the list and its sums are the loop's now
+    c->have_accel = false;
+    c->tgt_cand_valid = 0; c->bad_list_pass = -1;
+    const ActiveArgs A = jerk_args(c, &b.clock->n_active, &b.clock->stopped);
+    const int W = c->step_window;
+    for (int e = 0; e <= max_substeps; ++e) {
+        if (e >= W) {
+            const int seen = (e - W) % kStepWindowMax;
+            HIP_TRY(hipEventSynchronize(c->stop_ev[seen]));
+            if (c->stop_ring[seen]) break;
+        }
+        HIP_TRY(launch_active_accel_jerk(A, c->vel_all, s));
+        HIP_TRY(launch_hermite_correct(h, s));
+        HIP_TRY(launch_hermite_advance(h, s));
+        const int slot = e % kStepWindowMax;
+        if (!c->stop_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&c->stop_ev[slot], hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(&c->stop_ring[slot], &b.clock->stopped, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(c->stop_ev[slot], s));
+    }
     return NBX_OK;
 }
 

@@ -132,6 +132,20 @@ struct nbx_ctx {
     unsigned* block_flags = nullptr;         // [block_cap + 1]
     unsigned* block_tile_sums = nullptr;
     size_t block_cap = 0;
+    // accelerations and jerks of a list of targets (nbx_ctx_compute_accel_jerk_active) and the fourth-order Hermite loop
+    // (nbx_ctx_step_hermite_block; nbx_internal.h: HermiteArgs): made by the first call that needs them.  The list and its length
+    // word are active_list / active_count; the slice sums and folded sums have 2 dim planes and are these
+    float* vel_all = nullptr;                // [dim][pad] fp32 velocities of chunk 0, pads zero
+    double* jerk_part = nullptr;             // [slices][2 dim][stride], jerk_budget doubles
+    double* jerk_sums = nullptr;             // [2 dim][jerk_cap]
+    unsigned jerk_cap = 0;                   // = active_cap when the buffers were made
+    unsigned jerk_long_list = 0;             // lists from this length on run the jerk kernel's long-list build (NBODY_HIP_ACTIVE_LONG_LIST)
+    unsigned long long jerk_budget = 0;
+    size_t jerk_n = 0;                       // targets of the last nbx_ctx_compute_accel_jerk_active
+    bool have_jerk = false;                  // ... and its sums are on the device
+    double* hermite_a = nullptr;             // [dim][pad] a_i at t_i
+    double* hermite_j = nullptr;             // [dim][pad] j_i at t_i
+    unsigned long long* hermite_t = nullptr; // [count] t_i in ticks
 };
 
 namespace nbx {

@@ -330,8 +330,31 @@ struct ActiveArgs {
     int dim, law;                // law 0: m d / rho^4, 1: m d / rho^3; rho^2 = r^2 + eps2
     float eps2;
 };
+// What a launch looks like for the list as it stands: n targets, `stride` doubles between the planes of a slice (n in whole blocks
+// of 256), as many source slices as the buffer holds (at most the grid's), `tps` source tiles per slice.  `planes` sums are kept per
+// (target, slice): dim for the forces, 2 dim for the accelerations and jerks of active_jerk_kernel.hip.
+struct ActiveLayout { unsigned n, stride, slices, tps; };
+__device__ __forceinline__ ActiveLayout active_layout(const ActiveArgs& a, int planes) {
+    ActiveLayout s;
+    const unsigned listed = *a.count;
+    s.n = listed < a.cap ? listed : a.cap;
+    s.stride = s.n ? (s.n + 255u) / 256u * 256u : 256u;
+    unsigned long long fit = a.budget / ((unsigned long long)planes * s.stride);
+    if (fit > (unsigned long long)a.max_slices) fit = (unsigned long long)a.max_slices;
+    s.slices = fit ? (unsigned)fit : 1u;
+    const unsigned tiles = a.pad / (unsigned)kTile;
+    s.tps = (tiles + s.slices - 1u) / s.slices;
+    return s;
+}
 constexpr unsigned kActiveLongBlock = 2048;   // targets per workgroup of the long-list build: 256 lanes x 4 float2 pairs
 hipError_t launch_active_accel(const ActiveArgs& a, hipStream_t stream);
+// active_jerk_kernel.hip: the same evaluation with the time derivative.  a.part holds [slices][2 dim][stride] slice sums (a.budget >=
+// 2 dim * cap rounded up to 256), a.sums the folded [2 dim][cap] result, planes 0 .. dim-1 the acceleration sums, dim .. 2 dim-1 the
+// jerk sums; vel_all: chunk 0's fp32 velocities [dim][pad], pads zero.
+constexpr unsigned kJerkLongBlock = 1024;     // targets per workgroup of its long-list build: 256 lanes x 2 float2 pairs
+hipError_t launch_active_accel_jerk(const ActiveArgs& a, const float* vel_all, hipStream_t stream);
+// accel_out, jerk_out (either may be null): AoS double[*count][dim] on the device, row r = -(G sums[.][r])
+hipError_t launch_active_jerk_export(const ActiveArgs& a, double G, double* accel_out, double* jerk_out, hipStream_t stream);
 // forces_out: AoS double[*count][dim] on the device, row r = -(G m[list[r]]) sums[.][r]
 hipError_t launch_active_export(const ActiveArgs& a, double G, const double* m64, double* forces_out, hipStream_t stream);
 
@@ -376,6 +399,25 @@ hipError_t launch_block_kick(const BlockStepArgs& b, hipStream_t stream);
 hipError_t launch_block_advance(const BlockStepArgs& b, hipStream_t stream);
 // the active list for the clock's T as it stands (launch_block_advance ends with it; a call starts with it)
 hipError_t launch_block_select(const BlockStepArgs& b, hipStream_t stream);
+
+// ---- fourth-order Hermite with block time steps (nbx_ctx_step_hermite_block; include/nbody_hip.h has the rule) ----
+// The loop shares the block clock, both controllers, the levels and the select with the kick-drift-kick loop (b; b.sums is not
+// read).  Its own state: a, j at each body's own time t_i (in ticks), and the fp32 velocity chunk next to b.pos_chunk.
+struct HermiteArgs {
+    BlockStepArgs b;
+    const double* sums;             // [2 dim][b.cap]: launch_active_accel_jerk's folded sums of this evaluation
+    double* a64; double* j64;       // [dim][pad]
+    unsigned long long* t_i;        // [count]
+    float* vel_chunk;               // [dim][pad]
+    double eta, eta_start;
+};
+// vel_chunk = (float) v64 for the real bodies (the pads stay zero)
+hipError_t launch_hermite_refresh_velocities(const HermiteArgs& h, hipStream_t stream);
+// behind an evaluation's fold: the finiteness check of both sum sets, the controller's first half, then the first evaluation's
+// start (a, j, level, t_i = 0) or the corrector and the level choice of the active bodies
+hipError_t launch_hermite_correct(const HermiteArgs& h, hipStream_t stream);
+// the controller's second half, the predictor of ALL bodies into the fp32 chunks, the next active list
+hipError_t launch_hermite_advance(const HermiteArgs& h, hipStream_t stream);
 
 // forces_out: AoS double[count][dim] on the device
 hipError_t launch_export_forces(const float* acc, int splits, int dim, unsigned pad, size_t count,

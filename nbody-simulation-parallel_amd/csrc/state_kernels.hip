@@ -470,6 +470,123 @@ __global__ __launch_bounds__(256) void block_scatter_kernel(BlockStepArgs b) {
     if (b.flags[l + 1] != at) b.list[at] = (unsigned)l;
 }
 
+// ---- fourth-order Hermite with block time steps (nbx_ctx_step_hermite_block; include/nbody_hip.h has the rule) ----
+// Per evaluation the stream carries: the list kernels with the jerk and their fold (active_jerk_kernel.hip), then hermite_check,
+// block_control_pre, hermite_correct (launch_hermite_correct), then block_control_post, hermite_predict and the select pipeline
+// (launch_hermite_advance).  The clock, both controllers and the select are the kick-drift-kick loop's, unchanged.
+__global__ __launch_bounds__(256) void hermite_velocity_kernel(HermiteArgs h) {
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= h.b.count) return;
+    const size_t at = (size_t)blockIdx.y * h.b.pad + l;
+    h.vel_chunk[at] = (float)h.b.v64[at];
+}
+
+// "any component of a or j not finite: status 1, stop; nobody is corrected": the look at every active row comes before the corrector
+__global__ __launch_bounds__(256) void hermite_check_kernel(HermiteArgs h) {
+    BlockClock* const c = h.b.clock;
+    if (c->stopped) return;
+    const unsigned r = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    if (r < c->n_active)
+        for (int k = 0; k < 2 * h.b.dim; ++k) bad = bad || !(fabs(h.b.G * h.sums[(size_t)k * h.b.cap + r]) <= 1.7976931348623157e308);
+    const unsigned long long votes = __ballot(bad);
+    if ((threadIdx.x & 63u) == 0u && votes) atomicOr(&c->bad, 1u);
+}
+
+// One lane per active row.  The call's first evaluation starts every body: a, j, the level from eta_start |a| / |j|, t_i = 0.  Later
+// ones correct the body over its own step h = dt_level, choose its next level by Aarseth's criterion under the kick-drift-kick
+// loop's level rule, and leave (x, v, a, j) at t_i = T; the fp32 chunks take the corrected state (at T_end that is every body).
+__global__ __launch_bounds__(256) void hermite_correct_kernel(HermiteArgs h) {
+    const BlockStepArgs& b = h.b;
+    BlockClock* const c = b.clock;
+    if (c->apply == 0) return;
+    const unsigned r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= c->n_active) return;
+    const unsigned i = b.list[r];
+    const int L = c->levels;
+    const double dt_max = c->dt_max;
+    const unsigned long long T = c->T;
+    const bool first = c->first != 0, closing = c->closing != 0;
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    const int old = first ? -1 : b.level[i];
+    double a1[3], j1[3], sa = 0.0, sj = 0.0;
+    for (int k = 0; k < b.dim; ++k) {
+        a1[k] = -(b.G * h.sums[(size_t)k * b.cap + r]);
+        j1[k] = -(b.G * h.sums[(size_t)(b.dim + k) * b.cap + r]);
+        sa += a1[k] * a1[k];
+        sj += j1[k] * j1[k];
+    }
+    const double na = sqrt(sa), nj = sqrt(sj);
+    double raw;
+    if (first) {
+        raw = nj == 0.0 ? inf : (h.eta_start * na) / nj;
+    } else {
+        double dt = dt_max;
+        for (int l = 0; l < old; ++l) dt = 0.5 * dt;
+        const double h2 = dt * dt, h3 = h2 * dt;
+        double s2 = 0.0, s3 = 0.0;
+        for (int k = 0; k < b.dim; ++k) {
+            const size_t at = (size_t)k * b.pad + i;
+            const double a0 = h.a64[at], j0 = h.j64[at], v0 = b.v64[at], x0 = b.x64[at];
+            const double da = a0 - a1[k];
+            const double v1 = (v0 + (0.5 * dt) * (a0 + a1[k])) + (h2 / 12.0) * (j0 - j1[k]);
+            const double x1 = (x0 + (0.5 * dt) * (v0 + v1)) + (h2 / 12.0) * da;
+            const double a2 = (-6.0 * da - dt * (4.0 * j0 + 2.0 * j1[k])) / h2;
+            const double a3 = (12.0 * da + (6.0 * dt) * (j0 + j1[k])) / h3;
+            const double a2e = a2 + dt * a3;
+            s2 += a2e * a2e;
+            s3 += a3 * a3;
+            b.v64[at] = v1;
+            b.x64[at] = x1;
+            b.pos_chunk[at] = (float)x1;
+            h.vel_chunk[at] = (float)v1;
+        }
+        const double n2 = sqrt(s2), n3 = sqrt(s3);
+        const double den = nj * n3 + n2 * n2;
+        raw = den == 0.0 ? inf : sqrt((h.eta * (na * n2 + nj * nj)) / den);
+    }
+    for (int k = 0; k < b.dim; ++k) {
+        const size_t at = (size_t)k * b.pad + i;
+        h.a64[at] = a1[k];
+        h.j64[at] = j1[k];
+    }
+    h.t_i[i] = T;
+    int w = 0;
+    for (double d = dt_max; d > raw && w < L; ++w) d = 0.5 * d;
+    int now;
+    if (first) now = w;
+    else if (closing) now = old;
+    else if (w > old) now = w;
+    else if (w < old && old > 0 && (T & ((2ull << (L - old)) - 1ull)) == 0ull) now = old - 1;
+    else now = old;
+    if (now != old) {
+        b.level[i] = now;
+        atomicAdd(&c->pop[now], 1u);
+        if (old >= 0) atomicSub(&c->pop[old], 1u);
+    }
+}
+
+// The predictor of ALL bodies to the clock's T, into the fp32 chunks only: x, v themselves stay.  One lane per (body, component).
+__global__ __launch_bounds__(256) void hermite_predict_kernel(HermiteArgs h) {
+    const BlockClock* const c = h.b.clock;
+    if (c->drift == 0 && c->status != 2) return;
+    const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= h.b.count) return;
+    const size_t at = (size_t)blockIdx.y * h.b.pad + l;
+    if (c->drift == 0) {   // stopped at the cap: the bodies stay at their own times, and the fp32 chunks go back to being their roundings
+        h.b.pos_chunk[at] = (float)h.b.x64[at];
+        h.vel_chunk[at] = (float)h.b.v64[at];
+        return;
+    }
+    const double dt = (double)(c->T - h.t_i[l]) * c->tick;
+    const double h2 = dt * dt;
+    const double x = h.b.x64[at], v = h.b.v64[at], a = h.a64[at], j = h.j64[at];
+    const double xp = ((x + v * dt) + a * (0.5 * h2)) + j * ((h2 * dt) / 6.0);
+    const double vp = (v + a * dt) + j * (0.5 * h2);
+    h.b.pos_chunk[at] = (float)xp;
+    h.vel_chunk[at] = (float)vp;
+}
+
 __global__ __launch_bounds__(256) void export_forces_kernel(const float* __restrict__ acc, int splits, int dim,
                                                             unsigned pad, size_t count, double G,
                                                             const double* __restrict__ m64,
@@ -669,6 +786,25 @@ hipError_t launch_block_advance(const BlockStepArgs& b, hipStream_t stream) {
     if (b.count) hipLaunchKernelGGL(block_drift_kernel, dim3(blocks_for(b.count), (unsigned)b.dim, 1), dim3(256), 0, stream, b);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : launch_block_select(b, stream);
+}
+
+hipError_t launch_hermite_refresh_velocities(const HermiteArgs& h, hipStream_t stream) {
+    if (h.b.count) hipLaunchKernelGGL(hermite_velocity_kernel, dim3(blocks_for(h.b.count), (unsigned)h.b.dim, 1), dim3(256), 0, stream, h);
+    return hipGetLastError();
+}
+
+hipError_t launch_hermite_correct(const HermiteArgs& h, hipStream_t stream) {
+    if (h.b.count) hipLaunchKernelGGL(hermite_check_kernel, dim3(blocks_for(h.b.count)), dim3(256), 0, stream, h);
+    hipLaunchKernelGGL(block_control_pre_kernel, dim3(1), dim3(64), 0, stream, h.b.clock);
+    if (h.b.count) hipLaunchKernelGGL(hermite_correct_kernel, dim3(blocks_for(h.b.count)), dim3(256), 0, stream, h);
+    return hipGetLastError();
+}
+
+hipError_t launch_hermite_advance(const HermiteArgs& h, hipStream_t stream) {
+    hipLaunchKernelGGL(block_control_post_kernel, dim3(1), dim3(64), 0, stream, h.b.clock);
+    if (h.b.count) hipLaunchKernelGGL(hermite_predict_kernel, dim3(blocks_for(h.b.count), (unsigned)h.b.dim, 1), dim3(256), 0, stream, h);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_block_select(h.b, stream);
 }
 
 hipError_t launch_export_forces(const float* acc, int splits, int dim, unsigned pad, size_t count, double G,

@@ -53,7 +53,9 @@ struct Options {
     double dt_min = 0.0;            // --dt-min: kdka's smallest step (default: --dt / 1024)
     double t_end = std::numeric_limits<double>::infinity();   // --t-end: kdka stops there (default: after --steps steps)
     bool pow2 = false;              // --pow2: kdka's steps are --dt / 2^j
-    int levels = 8;                 // --levels L: kdkb's deepest level, a body's step is --dt / 2^level
+    int levels = 8;                 // --levels L: kdkb's and h4b's deepest level, a body's step is --dt / 2^level
+    double eta = 0.0;               // --eta e: h4b's accuracy parameter (Aarseth's step criterion)
+    double eta_start = 0.01;        // --eta-start s: the same for a call's first step, chosen from |a| / |j| alone
     std::string law = "reference";  // --law reference|newton: pair law of the stepping loop (newton: extension, needs --softening)
     double softening = 0.0;         // --softening eps: Plummer-softened law in the stepping loop (extension; 0 = reference law)
     std::vector<int> devices;       // --gpus / --devices: shard the HIP rows over these GPUs (one process)
@@ -626,7 +628,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
     }
 
     if (opt.steps > 0 && run_hip) {
-        out << "Leapfrog (kick-drift) on HIP: " << opt.steps << " steps" << (opt.integrator == "kdka" ? " at most (steps chosen on the device)" : opt.integrator == "kdkb" ? " (blocks of dt; a body steps by dt / 2^level, level chosen on the device)" : "")
+        out << "Leapfrog (kick-drift) on HIP: " << opt.steps << " steps" << (opt.integrator == "kdka" ? " at most (steps chosen on the device)" : opt.integrator == "kdkb" || opt.integrator == "h4b" ? " (blocks of dt; a body steps by dt / 2^level, level chosen on the device)" : "")
             << ", dt = " << opt.dt << ", G = " << opt.G;
         if (opt.softening > 0.0) out << ", softening = " << opt.softening;
         if (opt.law != "reference") out << ", law = " << opt.law;
@@ -642,7 +644,10 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
         unsigned ctx_taken = 0;
         // --integrator kdkb: chained calls of --energy-every blocks of --dt with block time steps (nbx_ctx_step_kdk_block); the row is
         // Leapfrog_HIP_<n>blocks_kdkb and a line behind the loop gives the substeps, the pair terms next to a shared step's, the deepest level
-        const bool ctx_kdkb = opt.integrator == "kdkb";
+        // --integrator h4b: the same chain through the fourth-order Hermite scheme (nbx_ctx_step_hermite_block); the row is
+        // Hermite_HIP_<n>blocks_h4b, with the same line
+        const bool ctx_h4b = opt.integrator == "h4b";
+        const bool ctx_kdkb = opt.integrator == "kdkb" || ctx_h4b;
         unsigned long long blk_substeps = 0, blk_terms = 0, blk_shared = 0;
         int blk_deepest = 0, blk_status = 0;
         double blk_t = 0.0;
@@ -674,7 +679,9 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
                 } else if (ctx_kdkb) {   // chained calls of k blocks: each ends with every body at one time, the next starts from fresh levels
                     nbx_block_control control{};
                     control.accel_length = opt.accel_length; control.dt_max = opt.dt; control.t_start = done * opt.dt; control.levels = opt.levels;
-                    const nbx_block_clock clock = sim.step_kdk_block(control, k);
+                    nbx_hermite_control hermite{};
+                    hermite.eta = opt.eta; hermite.eta_start = opt.eta_start; hermite.dt_max = opt.dt; hermite.t_start = done * opt.dt; hermite.levels = opt.levels;
+                    const nbx_block_clock clock = ctx_h4b ? sim.step_hermite_block(hermite, k) : sim.step_kdk_block(control, k);
                     blk_substeps += clock.substeps; blk_terms += clock.pair_terms;
                     blk_shared += (static_cast<unsigned long long>(clock.substeps) + 1ull) * static_cast<unsigned long long>(n) * static_cast<unsigned long long>(n);
                     blk_deepest = std::max(blk_deepest, clock.deepest_level); blk_status = clock.status; blk_t = clock.t;
@@ -698,7 +705,8 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
         });
         if (us >= 0) {
             const double seconds = static_cast<double>(us) / 1e6;
-            if (ctx_kdkb) csv << "Leapfrog_HIP_" << opt.steps << "blocks_kdkb," << n << "," << D;
+            if (ctx_h4b) csv << "Hermite_HIP_" << opt.steps << "blocks_h4b," << n << "," << D;
+            else if (ctx_kdkb) csv << "Leapfrog_HIP_" << opt.steps << "blocks_kdkb," << n << "," << D;
             else csv << "Leapfrog_HIP_" << opt.steps << "steps" << (ctx_kdka ? "_kdka" : "") << "," << n << "," << D;
             write_time(csv, seconds);
             if (opt.accuracy) csv << ",";
@@ -708,7 +716,7 @@ void run_benchmark(const std::vector<Body<D>>& bodies, const std::string& run_id
             if (ctx_kdkb)
                 out << "Block steps: " << blk_substeps << " substeps, t = " << std::setprecision(12) << blk_t << std::setprecision(6) << ", pair terms " << blk_terms
                     << " (a shared step: " << blk_shared << ", " << static_cast<double>(blk_shared) / static_cast<double>(blk_terms ? blk_terms : 1) << " x), deepest level "
-                    << blk_deepest << " of " << opt.levels << (blk_status == 1 ? "; stopped: an acceleration was not finite" : "") << std::endl;
+                    << blk_deepest << " of " << opt.levels << (blk_status == 1 ? (ctx_h4b ? "; stopped: an acceleration or jerk was not finite" : "; stopped: an acceleration was not finite") : "") << std::endl;
             if (!opt.dump.empty()) dump_raw(opt.dump + "_Leapfrog_HIP.f64", state);
             out << "Body #1 position: (";
             for (int d = 0; d < D; ++d) out << state[0].position[d] << (d < D - 1 ? ", " : "");
@@ -746,6 +754,8 @@ void usage(const char* argv0) {
               << "                      kdkb (-m g on one GPU, needs --softening) = kick-drift-kick with block time steps: --steps blocks of --dt, a body steps by" << std::endl
               << "                      --dt / 2^level with its level in [0, --levels L] (default 8) chosen on the device from its own acceleration and --accel-length;" << std::endl
               << "                      only the bodies whose step ends are evaluated; the row is Leapfrog_HIP_<n>blocks_kdkb" << std::endl
+              << "                      h4b (-m g on one GPU, needs --softening) = fourth-order Hermite with the same block time steps: levels chosen by Aarseth's" << std::endl
+              << "                      criterion with --eta <e> (--eta-start <s>, default 0.01, for a call's first step); the row is Hermite_HIP_<n>blocks_h4b" << std::endl
               << "      --law <reference|newton> Pair law of the stepping loop: the reference's r^-4 form (default) or the attractive" << std::endl
               << "                      softened Newtonian law (extension; needs --softening; Plummer velocities then use --G)" << std::endl
               << "                      with -m t: BarnesHut_HIP_newton rows behind the reference-law rows, judged against the all-pairs forces" << std::endl
@@ -826,12 +836,16 @@ int main(int argc, char* argv[]) {
             opt.softening = std::stod(argv[++i]);
         } else if (arg == "--integrator" && has_value) {
             opt.integrator = argv[++i];
-            if (opt.integrator != "kd" && opt.integrator != "kdk" && opt.integrator != "kdka" && opt.integrator != "kdkb") {
-                std::cerr << "Error: --integrator must be kd, kdk, kdka or kdkb" << std::endl;
+            if (opt.integrator != "kd" && opt.integrator != "kdk" && opt.integrator != "kdka" && opt.integrator != "kdkb" && opt.integrator != "h4b") {
+                std::cerr << "Error: --integrator must be kd, kdk, kdka, kdkb or h4b" << std::endl;
                 return 1;
             }
         } else if (arg == "--accel-length" && has_value) {
             opt.accel_length = std::stod(argv[++i]);
+        } else if (arg == "--eta" && has_value) {
+            opt.eta = std::stod(argv[++i]);
+        } else if (arg == "--eta-start" && has_value) {
+            opt.eta_start = std::stod(argv[++i]);
         } else if (arg == "--dt-min" && has_value) {
             opt.dt_min = std::stod(argv[++i]);
         } else if (arg == "--t-end" && has_value) {
@@ -915,6 +929,16 @@ int main(int argc, char* argv[]) {
         }
         if (!(opt.accel_length > 0.0) || !(opt.softening > 0.0) || opt.levels < 0 || opt.levels > 20) {
             std::cerr << "Error: --integrator kdkb needs --accel-length c > 0, --softening eps > 0 and --levels in [0, 20]" << std::endl;
+            return 1;
+        }
+    }
+    if (opt.integrator == "h4b") {
+        if (opt.methods.find('g') == std::string::npos || opt.methods.find_first_of("atp") != std::string::npos || opt.devices.size() > 1) {
+            std::cerr << "Error: --integrator h4b drives the all-pairs loop on one GPU (-m g): leave --gpus / --devices out" << std::endl;
+            return 1;
+        }
+        if (!(opt.eta > 0.0) || !(opt.eta_start > 0.0) || !(opt.softening > 0.0) || opt.levels < 0 || opt.levels > 20) {
+            std::cerr << "Error: --integrator h4b needs --eta e > 0 (and --eta-start s > 0 where given), --softening eps > 0 and --levels in [0, 20]" << std::endl;
             return 1;
         }
     }

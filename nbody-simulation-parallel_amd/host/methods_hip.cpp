@@ -274,6 +274,24 @@ nbx_block_clock HipSimulation<D>::step_kdk_block(const nbx_block_control& contro
     return clock;
 }
 template <int D>
+nbx_block_clock HipSimulation<D>::step_hermite_block(const nbx_hermite_control& control, int n_blocks, int max_substeps) {
+    if (!ctx_) throw std::runtime_error("HipSimulation::step_hermite_block: the simulation is sharded over several devices; block time steps need one GPU");
+    nbx_block_clock clock{};
+    int rc = nbx_ctx_step_hermite_block(ctx_, G_, &control, n_blocks, max_substeps);
+    if (!rc && n_blocks > 0) rc = nbx_ctx_get_block_clock(ctx_, &clock);
+    if (rc != NBX_OK) raise("HipSimulation::step_hermite_block", rc);
+    return clock;
+}
+template <int D>
+void HipSimulation<D>::accel_jerk_active(const std::vector<uint32_t>& targets, std::vector<Vector<D>>& accel, std::vector<Vector<D>>& jerk) {
+    if (!ctx_) throw std::runtime_error("HipSimulation::accel_jerk_active: the simulation is sharded over several devices; the list kernels need one GPU");
+    accel.resize(targets.size());
+    jerk.resize(targets.size());
+    int rc = nbx_ctx_compute_accel_jerk_active(ctx_, targets.data(), targets.size());
+    if (!rc) rc = nbx_ctx_get_accel_jerk_active(ctx_, G_, reinterpret_cast<double*>(accel.data()), reinterpret_cast<double*>(jerk.data()));
+    if (rc != NBX_OK) raise("HipSimulation::accel_jerk_active", rc);
+}
+template <int D>
 void HipSimulation<D>::step_range(double& dt_smallest, double& dt_largest) {
     if (!ctx_) throw std::runtime_error("HipSimulation::step_range: the simulation is sharded over several devices; steps chosen on the device need one GPU");
     dt_smallest = dt_largest = 0.0;

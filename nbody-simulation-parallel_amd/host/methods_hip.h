@@ -78,6 +78,11 @@ public:
     // dt_max / 2^level, only the bodies whose step ends are evaluated; returns the device's clock (which synchronises).  One GPU, a
     // softening length > 0.
     nbx_block_clock step_kdk_block(const nbx_block_control& control, int n_blocks, int max_substeps = 1 << 20);
+    // extension: the fourth-order Hermite scheme with the same block time steps (nbx_ctx_step_hermite_block), levels chosen by
+    // Aarseth's criterion; and the accelerations F / m and jerks of a list of bodies against all bodies, an observer
+    // (nbx_ctx_compute_accel_jerk_active / _get_accel_jerk_active).  One GPU, a softening length > 0.
+    nbx_block_clock step_hermite_block(const nbx_hermite_control& control, int n_blocks, int max_substeps = 1 << 20);
+    void accel_jerk_active(const std::vector<uint32_t>& targets, std::vector<Vector<D>>& accel, std::vector<Vector<D>>& jerk);
     double max_accel();
     void step_range(double& dt_smallest, double& dt_largest);   // over the steps of the last step_kdk_adaptive call (0, 0: it took none)
     void energy(double& kinetic, double& potential);  // of the whole system, under the reference law's potential
